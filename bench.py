@@ -8,8 +8,14 @@ launch, and the autoreset launch that re-initialises finished boards
 (seed += stride); for N > 1 also the RCCL all-gather of packed
 reward/truncated/done over xGMI. Inputs are resident in HBM before timing.
 
-    python bench.py [--gpus N --steps K --warmup W --boards B]
+    python bench.py [--gpus N --steps K --warmup W --boards B] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU)
+
+A plain run does only what the headline figure needs: set up, warm up, time
+the K steps, write the last step's outputs if --dump-outputs is given, print
+the result line. --full adds everything else to the line: the per-kernel HIP
+event timing and the roofline, the state digest and the C-oracle replay of
+timed boards (parity), the N > 1 gather check and the CPU baseline.
 
 `python bench.py --gpus N` without a launcher starts N rank processes itself
 (one per GPU, LOCAL_RANK = device) from a parent that never touches the GPU;
@@ -239,6 +245,30 @@ def state_digest(env):
     return f"{c:08x}"
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs writes less than this in all (the limit is 64 MB)
+
+
+def dump_outputs(env, directory):
+    """--dump-outputs: what the last timed step returned (observation, reward, done, truncated,
+    flags) and left behind (score, moves, seed, pre-drawn next action) for a fixed, seeded sample
+    of the boards (all of them when they fit the budget), one DIR/<name>.npy each, float32
+    (seeds, which pass 2**24, and the sampled board indices: float64)."""
+    import numpy as np
+
+    n = env.n
+    per_board = 4 * env.rows * env.columns + 4 * 7 + 8 * 2
+    k = min(n, DUMP_BUDGET_BYTES // per_board)
+    idx = np.arange(n) if k == n else np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+    os.makedirs(directory, exist_ok=True)
+    arrays = {"observations": env.observations(), "rewards": env.rewards(), "dones": env.dones(),
+              "truncateds": env.truncateds(), "flags": env.flags(), "scores": env.scores(), "moves": env.moves(),
+              "next_actions": env.next_actions()}
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a[idx].astype(np.float32))
+    np.save(os.path.join(directory, "seeds.npy"), env.seeds()[idx].astype(np.float64))
+    np.save(os.path.join(directory, "board_index.npy"), idx.astype(np.float64))
+
+
 SHUFFLE_CAP_FLAG = 0x04  # M3_FLAG_SHUFFLE_CAP (include/m3.h), also the oracle's
 
 
@@ -385,6 +415,13 @@ def main():
                          "after every step (step); both inside the timed region")
     ap.add_argument("--allow-stale-lib", action="store_true",
                     help="if `make` fails, time the library already built (recorded as build.stale in the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (rank 0's boards, a fixed seeded "
+                         "sample when they exceed the size budget) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: per-kernel event timing "
+                         "and roofline, state digest and oracle replay (--check-boards), the N > 1 gather check, "
+                         "the CPU baseline (--cpu-seconds, --no-cpu-baseline)")
     args = ap.parse_args()
     if args.hw_queues is not None:
         if not 1 <= args.hw_queues <= 32:
@@ -430,12 +467,14 @@ def main():
     # A/B variants are separate files (make variant), selected with M3_LIB (then nothing is
     # built). The ranks of one node share the tree: they take turns under a file lock, so at
     # most one builds. A failed build stops the bench unless --allow-stale-lib.
+    # A tree this user cannot write to (built by someone else) cannot be rebuilt: its library is timed as it is.
     build = {"library": os.environ.get("M3_LIB", os.path.join(PKG, "build", "libm3.so")), "make_rc": None,
              "stale": False}
-    if "M3_LIB" not in os.environ:
+    bdir = os.path.join(PKG, "build")
+    if "M3_LIB" not in os.environ and os.access(bdir if os.path.isdir(bdir) else PKG, os.W_OK):
         import fcntl
 
-        os.makedirs(os.path.join(PKG, "build"), exist_ok=True)
+        os.makedirs(bdir, exist_ok=True)
         with open(os.path.join(PKG, "build", ".make.lock"), "w") as lk:
             fcntl.flock(lk, fcntl.LOCK_EX)
             r = subprocess.run(["make", "-s", "-C", PKG])
@@ -465,26 +504,29 @@ def main():
 
     step, final_gather = step_fns(env, world, args.gather)
     elapsed, elapsed_local = timed_steps(step, env.synchronize, args.steps, args.warmup, dist,
-                                         on_start=lambda: env.enable_timing(args.steps), on_end=final_gather,
-                                         return_local=True)
+                                         on_start=(lambda: env.enable_timing(args.steps)) if args.full else None,
+                                         on_end=final_gather, return_local=True)
     rank_ms = dist.allgather_obj(elapsed_local / args.steps * 1e3) if dist else [elapsed_local / args.steps * 1e3]
-    kms = env.kernel_ms()
-    kms_step = env.kernel_ms(step_kernel_only=True)
     stats = env.stats()
-    # ---- after the clock: attest the run (nothing below is timed) ----
     nranks = env.comm_size()
-    gather_ok = gather_check(env, dist, rank, world) if dist else None
-    parity = {"digest": state_digest(env)}
-    if dist:
-        parity["digest_all_ranks"] = dist.allgather_obj(parity["digest"])
-    if args.check_boards and not args.no_autoreset:
-        chk = oracle_sample_check(env, (rows, cols, types), args.moves, args.goal, seed_base, seed_stride,
-                                  args.warmup + args.steps, args.check_boards)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(env, args.dump_outputs)
+    if args.full:
+        kms = env.kernel_ms()
+        kms_step = env.kernel_ms(step_kernel_only=True)
+        # ---- after the clock: attest the run (nothing below is timed) ----
+        gather_ok = gather_check(env, dist, rank, world) if dist else None
+        parity = {"digest": state_digest(env)}
         if dist:
-            nb, nm, nc = dist.allsum([chk["boards"], chk["mismatches"], chk["shuffle_capped"]])
-            chk.update(boards=nb, mismatches=nm, shuffle_capped=nc, ranks=world)
-        parity["oracle_sample"] = chk
-        parity["oracle_match"] = chk["mismatches"] == 0 and chk["boards"] > 0
+            parity["digest_all_ranks"] = dist.allgather_obj(parity["digest"])
+        if args.check_boards and not args.no_autoreset:
+            chk = oracle_sample_check(env, (rows, cols, types), args.moves, args.goal, seed_base, seed_stride,
+                                      args.warmup + args.steps, args.check_boards)
+            if dist:
+                nb, nm, nc = dist.allsum([chk["boards"], chk["mismatches"], chk["shuffle_capped"]])
+                chk.update(boards=nb, mismatches=nm, shuffle_capped=nc, ranks=world)
+            parity["oracle_sample"] = chk
+            parity["oracle_match"] = chk["mismatches"] == 0 and chk["boards"] > 0
     env.close()
 
     if rank != 0:
@@ -494,6 +536,44 @@ def main():
     total_steps = world * B * args.steps
     value = total_steps / elapsed
     step_s = elapsed / args.steps
+    out = {
+        "metric": METRIC,
+        "value": value,
+        "unit": "env-steps/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "int8",
+        "data": "synthetic: seeded initial boards (seed = 1 + board index), seeded random_action per move "
+                "(samplerTasks.random_task contract), 20-move episodes, autoreset with seed += n_boards",
+        "config": {
+            "workload": f"{'C3' if (rows, cols) == (9, 9) else 'C4'}: {B:,} boards per GPU, {rows}x{cols}x{types}, Match3Env.step x {args.steps} "
+                        "(step kernel + overflow fixup + autoreset; N>1: RCCL reward/done all-gather "
+                        + ("once after the last step" if args.gather == "final" else "after every step") + ")",
+            "boards_per_gpu": B,
+            "shape": args.shape,
+            "num_moves": args.moves,
+            "env_goal": args.goal,
+            "parallelism": f"dp{world}",
+            "shards_per_gpu": stats["shards"],
+            "hw_queues": args.hw_queues,
+            "autoreset": not args.no_autoreset,
+        },
+        "nranks": nranks,
+        "gather": (args.gather if world > 1 else None),
+        "ms_per_step_per_rank": rank_ms,
+        "build": build,
+        "full": args.full,
+    }
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        dist_close(dist, rank)
+        return
+
     avg_kernel_s = float(kms.mean()) / 1e3 if len(kms) else float("nan")
     avg_step_kernel_s = float(kms_step.mean()) / 1e3 if len(kms_step) else float("nan")
     # one launch of the step pipeline processes one shard (B / shards boards, contiguous, the last may be short)
@@ -546,43 +626,13 @@ def main():
             "hbm": hbm, "pipeline": pipeline}
     else:
         roofline = dict(hbm, bound="hbm", valu=None, hbm=hbm, pipeline=pipeline)
-    out = {
-        "metric": METRIC,
-        "value": value,
-        "unit": "env-steps/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "int8",
-        "data": "synthetic: seeded initial boards (seed = 1 + board index), seeded random_action per move "
-                "(samplerTasks.random_task contract), 20-move episodes, autoreset with seed += n_boards",
-        "config": {
-            "workload": f"{'C3' if (rows, cols) == (9, 9) else 'C4'}: {B:,} boards per GPU, {rows}x{cols}x{types}, Match3Env.step x {args.steps} "
-                        "(step kernel + overflow fixup + autoreset; N>1: RCCL reward/done all-gather "
-                        + ("once after the last step" if args.gather == "final" else "after every step") + ")",
-            "boards_per_gpu": B,
-            "shape": args.shape,
-            "num_moves": args.moves,
-            "env_goal": args.goal,
-            "parallelism": f"dp{world}",
-            "shards_per_gpu": stats["shards"],
-            "hw_queues": args.hw_queues,
-            "autoreset": not args.no_autoreset,
-        },
-        "nranks": nranks,
-        "gather": (args.gather if world > 1 else None),
-        "ms_per_step_per_rank": rank_ms,
+    out.update({
         "gather_ok": gather_ok,
         "parity": parity,
         "path_stats": {"autoresets": stats["autoresets"], "reset_recomputes": stats["reset_recomputes"],
                        "step_recomputes": stats["step_recomputes"]},
         "roofline": roofline,
-        "build": build,
-    }
+    })
     if world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(rows, cols, types, args.moves, args.goal, args.cpu_seconds)
     print(json.dumps(out), flush=True)

@@ -17,8 +17,8 @@ for round in 1 2; do
   for L in libm3.so "$@"; do
     CHK=64; case $L in *nopf*) CHK=0;; esac
     export M3_LIB=$PWD/element-crush-gym_amd/build/$L
-    timeout -k 10 300 python3 bench.py --steps 40 --warmup 10 --no-cpu-baseline --check-boards $CHK > $O/b9_${L}_$round.log 2>&1 || exit 1
-    timeout -k 10 300 python3 bench.py $S16 --steps 40 --warmup 10 --no-cpu-baseline --check-boards $CHK > $O/b16_${L}_$round.log 2>&1 || exit 1
+    timeout -k 10 300 python3 bench.py --full --steps 40 --warmup 10 --no-cpu-baseline --check-boards $CHK > $O/b9_${L}_$round.log 2>&1 || exit 1
+    timeout -k 10 300 python3 bench.py --full $S16 --steps 40 --warmup 10 --no-cpu-baseline --check-boards $CHK > $O/b16_${L}_$round.log 2>&1 || exit 1
   done
 done
 unset M3_LIB

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 TAG=${1:-dev}; SH=${2:-9}
 if [ "$SH" = 16 ]; then A="--shape 16x16x8 --boards 262144"; O=gpurun_out/$TAG/s16; else A=""; O=gpurun_out/$TAG/s9; fi
 mkdir -p $O
-B="bench.py --gpus 1 --steps 20 --warmup 5 $A"
+B="bench.py --gpus 1 --steps 20 --warmup 5 --full $A"
 timeout -k 10 300 python3 $B > $O/bench.log 2>&1 || exit 1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/kt -o kt --output-format csv -- python3 $B --no-cpu-baseline > $O/kt.log 2>&1 || exit 1
 pass() {  # name counters...

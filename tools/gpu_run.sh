@@ -16,8 +16,8 @@ for step in "$@"; do
     smoke) timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 ;;
     tests) timeout -k 10 1100 python3 -u -m pytest tests -m gpu -x -v --timeout 400 --timeout-method thread > $O/gpu_tests.log 2>&1 ;;
     tests:*) timeout -k 10 900 python3 -u -m pytest ${step#tests:} -m gpu -x -v --timeout 400 --timeout-method thread > $O/tests_$n.log 2>&1 ;;
-    bench9) timeout -k 10 300 python3 bench.py > $O/bench9_$n.log 2>&1 ;;
-    bench16) timeout -k 10 300 python3 bench.py --shape 16x16x8 --boards 262144 --steps 40 --warmup 10 > $O/bench16_$n.log 2>&1 ;;
+    bench9) timeout -k 10 300 python3 bench.py --full > $O/bench9_$n.log 2>&1 ;;
+    bench16) timeout -k 10 300 python3 bench.py --full --shape 16x16x8 --boards 262144 --steps 40 --warmup 10 > $O/bench16_$n.log 2>&1 ;;
     *) echo "unknown step $step"; exit 2 ;;
   esac
   rc=$?
