@@ -285,7 +285,11 @@ int m3_ctx_create(int device, int rows, int columns, int types, m3_ctx** out) {
     c->sdesc = make_shape(rows, columns, types);
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipMalloc(&c->counters, 256);
-    if (e == hipSuccess) e = hipMemset(c->counters, 0, 256);  // (the zero-copy overflow word starts at zero)
+    // (the zero-copy overflow word starts at zero.) On the context's own stream, and finished before
+    // the context is handed out: hipMemset runs on the null stream and may return before the fill is
+    // done, and the context stream is non-blocking, so it does not wait for the null stream
+    if (e == hipSuccess) e = hipMemsetAsync(c->counters, 0, 256, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
         delete c;
         return set_err(M3_ERR_HIP, "context setup: %s", hipGetErrorString(e));
@@ -454,8 +458,8 @@ int m3_apply_actions(m3_ctx* c, int64_t n, const int8_t* boards, const uint32_t*
         rc = with_shape(c->shape, [&](auto cf) { return launch_apply<decltype(cf)>(c, a); });
         if (rc) {  // k_apply may have counted overflows that k_apply_fix never cleared: the next
                    // call must not read them (best effort; the launch error is what is reported)
+            (void)hipMemsetAsync(a.ovf_count, 0, 4, c->stream);  // (ordered before the next call's kernels)
             (void)hipStreamSynchronize(c->stream);
-            (void)hipMemset(a.ovf_count, 0, 4);
             return rc;
         }
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -716,13 +720,18 @@ int m3_env_create(m3_ctx* c, int64_t n, int num_moves, int env_goal, m3_env** ou
     });
     for (hipEvent_t& ev : e->gev)
         if (err == hipSuccess) err = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    // every per-board field starts zeroed: a never-reset env reads back zeros, not stale device memory
+    // every per-board field starts zeroed: a never-reset env reads back zeros, not stale device memory.
+    // The fills go to the context stream and are finished before the env is handed out. As hipMemset
+    // calls they ran on the null stream, which may return before the fill is done and which the
+    // non-blocking context and shard streams do not wait for: a fill could land after m3_env_reset's
+    // seed upload on the context stream, and the first boards of the env then reset from seed 0.
     {
         void* zp[] = {e->boards[0], e->boards[1], e->seeds, e->flags, e->draws, e->legal, e->score, e->moves,
                       e->next_action, e->reward, e->done, e->trunc, e->slot};
         size_t zb[] = {bytes, bytes, n * 4ull, n * 4ull, n * 4ull, n * 4ull * c->AW, n * 4ull, n * 4ull,
                        n * 4ull, n * 4ull, (size_t)n, (size_t)n, (size_t)n};
-        for (int i = 0; i < 13 && err == hipSuccess; ++i) err = hipMemset(zp[i], 0, zb[i]);
+        for (int i = 0; i < 13 && err == hipSuccess; ++i) err = hipMemsetAsync(zp[i], 0, zb[i], c->stream);
+        if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
     }
     if (err != hipSuccess) {
         m3_env_destroy(e);
@@ -1126,7 +1135,7 @@ int m3_env_stats(m3_env* e, uint64_t out[4]) {
     out[0] = out[1] = out[2] = out[3] = 0;
     for (size_t s = 0; s < e->shards.size(); ++s) {
         out[0] += h[64 * s + 40];  // steps recomputed (cache exhausted or > table groups)
-        out[1] += h[64 * s + 42];  // resets recomputed by the wave-cooperative pass (>= 624 draws)
+        out[1] += h[64 * s + 42];  // resets recomputed by the wave-cooperative pass (see include/m3.h)
         out[2] += h[64 * s + 41];  // autoresets (episodes prefetched)
     }
     out[3] = e->shards.size();

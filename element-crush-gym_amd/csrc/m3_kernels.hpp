@@ -59,7 +59,7 @@ constexpr int INIT_BLOCK = 64;
 #endif
 template <class CF>
 constexpr uint32_t lanes_for() { return CF::W > 8 ? (uint32_t)M3_WIDE_FRAME_LANES : 64u; }
-// 9x9: k_init redoes its few >= 624-draw resets in-wave (wave_reset); 16x16
+// 9x9: k_init redoes its few > 624-draw resets in-wave (wave_reset); 16x16
 // resets go straight to k_init_fix_lane (most need >= 624 draws)
 template <class CF>
 constexpr bool INIT_INLINE_FIX = CF::N <= 128;
@@ -677,10 +677,10 @@ struct InitArgs {
     uint8_t* trunc;
     uint32_t* flags;
     uint32_t* slot_flags;        // nullable: M3_FLAG_RESET_CAP of the reset at ob (env episode slots), else 0
-    uint32_t* stats;             // nullable: [0] resets, [1] reset recomputes (>= 624 draws)
+    uint32_t* stats;             // nullable: [0] resets, [1] reset recomputes (past the draw cap / the ring)
     uint32_t* m397;              // nullable: mt[397] of the seed's init_genrand state at (slot, b)
     int64_t cstride;
-    uint32_t* defer;             // nullable: items k_init leaves to k_init_coop (reset needs >= RESET_KCAP draws)
+    uint32_t* defer;             // nullable: items k_init leaves to k_init_coop (reset needs > RESET_KCAP draws)
     uint32_t* defer_count;       // device count for defer (zeroed before k_init)
     uint32_t* tab;               // nullable: two-stage reset table rows [n][TwoStage::TW] (16x16x8 prefetch)
 };
@@ -749,7 +749,7 @@ __device__ __forceinline__ void init_outputs(const InitArgs& a, int64_t b, int64
 }
 
 // Reset of board b on a tile stream generated in LDS (init_board_tiles).
-// Returns false if the reset needs >= kcap draws (wave_reset redoes it).
+// Returns false if the reset needs > kcap draws (exactly kcap still fits) or overran the ring: redone.
 template <class CF, class S = NoStore>
 __device__ __forceinline__ bool init_emit(const InitArgs& a, int64_t b, uint32_t seed, uint32_t slot, uint32_t m397,
                                           uint32_t* tm, uint32_t* pos, S* ps = nullptr, uint32_t kcap = 624u) {
@@ -767,7 +767,7 @@ __device__ __forceinline__ bool init_emit(const InitArgs& a, int64_t b, uint32_t
     return true;
 }
 
-// ---- wave-cooperative reset for boards whose reset needs >= 624 draws ----
+// ---- wave-cooperative reset for boards whose reset needs > 624 draws ----
 // One board per wave. The 624-word MT19937 state sits in LDS; the twist runs
 // on all 64 lanes (three dependency phases), and randint(1, T+1) over the
 // board is a parallel filter: 64 raw outputs per trip, ballot of the accepted
@@ -902,9 +902,9 @@ __device__ uint32_t wave_reset(const InitArgs& a, int64_t item, uint32_t* key, u
 }
 
 // Reset on the register-only MT19937 chain; grid-strided over n (or *list_count).
-// A reset that needs >= 624 draws (~0.7 % at 9x9x6) is redone by its own wave
+// A reset that needs > 624 draws (~0.7 % at 9x9x6) is redone by its own wave
 // right away (wave_reset).
-// REDO: the explicit-reset form, whose wave redoes its >= 624-draw resets itself (wave_reset, 2.5 KB
+// REDO: the explicit-reset form, whose wave redoes its > 624-draw resets itself (wave_reset, 2.5 KB
 // of LDS for the MT state); the env prefetch (a.defer) defers them to k_init_coop instead and leaves
 // that LDS out, so with the 10-word tile ring its wave takes ~10 KB -- what a CU full of k_env_step waves
 // (16 x 9 KB) still has free.
@@ -954,7 +954,7 @@ __global__ void __launch_bounds__(INIT_BLOCK) k_init(InitArgs a) {
             }
             continue;
         }
-        // this wave redoes its >= 624-draw resets at once
+        // this wave redoes its > 624-draw resets at once
         if (bad && a.stats && threadIdx.x == 0) atomicAdd(&a.stats[1], (uint32_t)__builtin_popcountll(bad));
         if constexpr (REDO) {
             while (bad) {
@@ -969,7 +969,7 @@ __global__ void __launch_bounds__(INIT_BLOCK) k_init(InitArgs a) {
 #endif
 }
 
-// The resets k_init deferred (>= RESET_KCAP draws), one wave per board
+// The resets k_init deferred (> RESET_KCAP draws, or a ring overrun), one wave per board
 // (wave_reset), grid-strided over the device-side count.
 template <class CF>
 __global__ void __launch_bounds__(64) k_init_coop(InitArgs a) {

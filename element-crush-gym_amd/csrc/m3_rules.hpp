@@ -273,10 +273,13 @@ struct FrameDim {
     M3_HD Bd valid() const { return vmask; }
 };
 
-// wave-wide "any" (host build: the lane itself)
+// wave-wide "any" (host build: the lane itself; the test harness may stand in for the other lanes
+// of the wave with M3_HOST_WAVE_ANY, defined before this header -- the library never defines it)
 M3_HD bool wave_any(bool p) {
 #ifdef __HIP_DEVICE_COMPILE__
     return __any((int)p) != 0;
+#elif defined(M3_HOST_WAVE_ANY)
+    return M3_HOST_WAVE_ANY(p);
 #else
     return p;
 #endif

@@ -215,7 +215,11 @@ int m3_env_debug_stall(m3_env *env, uint32_t usec);
 
 /* Cumulative counters since the last m3_env_reset: out[0] steps recomputed on
  * the exact fallback pass (>= 624 MT draws or more match groups than the LDS
- * table), out[1] resets recomputed by the wave-cooperative pass (>= 624 draws),
+ * table), out[1] resets recomputed by the wave-cooperative pass (9x9x6: a
+ * reset of more than 624 MT draws -- exactly 624 still fits the register chain
+ * -- or, when an autoreset's prefetch built it, of more than 454, or one whose
+ * tile ring would have overrun; other shapes: the resets past what their
+ * fast reset kernel covers, 624 draws or more on the explicit-reset path),
  * out[2] autoresets, out[3] number of shards. */
 int m3_env_stats(m3_env *env, uint64_t out[4]);
 

@@ -96,6 +96,52 @@ static int run(int cfg, int R, int C, int T, int BITS, uint32_t& rs, long& check
     return 0;
 }
 
+// The 9x9x6 tile-stream reset at the deferral boundary (draw caps below the MT block) and on the
+// 7-word ring (hc_init9_kcap / hc_init9_ring7: tm and pos are exactly the ring's size there, so an
+// index past it is a report): every reset that finished must equal the scalar reset, and so must
+// every one redone by the fallback.
+static int run_reset_ring(uint32_t& rs, long& checks) {
+    long n = getenv("HC_N") ? atol(getenv("HC_N")) : 96;
+    if (n < 96) n = 96;  // (resets alone are cheap: enough of them that both ring branches run)
+    constexpr int N = 81;
+    std::vector<uint32_t> seeds(n);
+    std::vector<int8_t> want(n * N), got(n * N);
+    std::vector<int32_t> dw(n), dg(n);
+    std::vector<uint8_t> ok(n);
+    for (long i = 0; i < n; ++i) seeds[i] = lcg(&rs) * 977u + 1u;
+    hc_init_scalar(0, n, seeds.data(), want.data(), dw.data());
+    // {draw cap, neighbour}: with a neighbour lane that keeps the wave drawing up to the cap, the
+    // lane's unread tiles reach the ring's limit (the overrun exit of the shipped 10-word ring)
+    static const uint32_t caps[][2] = {{81u, 0}, {200u, 0}, {454u, 0}, {455u, 0}, {623u, 0}, {624u, 0},
+                                       {624u, 16}, {454u, 16}, {624u, 3}};
+    for (const auto& cap : caps) {
+        const uint32_t kcap = cap[0];
+        const int neighbour = (int)cap[1];
+        if (hc_init9_kcap(n, seeds.data(), kcap, neighbour, got.data(), dg.data(), ok.data()) < 0)
+            return fail("kcap", 0, kcap);
+        for (long i = 0; i < n; ++i) {
+            if (ok[i] && (uint32_t)dw[i] > kcap) return fail("kcap: finished a reset past the cap", 0, i);
+            if (!neighbour && !ok[i] && (uint32_t)dw[i] <= kcap) return fail("kcap: gave up a reset within the cap", 0, i);
+            if (!ok[i]) continue;
+            if (dg[i] != dw[i]) return fail("kcap: draws", 0, i);
+            for (int x = 0; x < N; ++x)
+                if (got[i * N + x] != want[i * N + x]) return fail("kcap: board", 0, i);
+        }
+    }
+    for (int neighbour : {0, 1, 16}) {
+        const int fell = hc_init9_ring7(n, seeds.data(), neighbour, got.data(), dg.data(), ok.data());
+        if (fell <= 0 || (!neighbour && fell >= n))
+            return fail("ring7: both the overrun exit and the ring path must run", 0, fell);
+        for (long i = 0; i < n; ++i) {
+            if (dg[i] != dw[i]) return fail("ring7: draws", 0, i);
+            for (int x = 0; x < N; ++x)
+                if (got[i * N + x] != want[i * N + x]) return fail("ring7: board", 0, i);
+        }
+    }
+    checks += n;
+    return 0;
+}
+
 int main() {
     uint32_t rs = 2024u;
     long checks = 0;
@@ -111,6 +157,7 @@ int main() {
         printf("frame %dx%dx%d done\n", f[0], f[1], f[2]);
         fflush(stdout);
     }
+    if (run_reset_ring(rs, checks)) return 1;
     printf("hostcore asan: %ld boards through every entry point, no sanitizer report\n", checks);
     return 0;
 }

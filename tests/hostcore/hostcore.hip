@@ -8,6 +8,19 @@
 // configs), cfg 2 = the frame (FCfg: 16 x 16, or 32 x 32 for a side > 16) for
 // the board set by hc_set_frame(rows, columns, types) -- any shape, including
 // 9x9x6 / 16x16x8.
+// The other lanes of the wave, for the code that runs in lockstep with them (wave_any): on the GPU a
+// lane whose own vote is false keeps going while any other lane of its wave still votes true. Here
+// the stand-in neighbour outvotes the lane g_neighbour_votes times (0: the lane is alone, as in
+// every entry point but the reset ones that set it) -- in init_board_tiles each vote is one more
+// 64-draw chunk generated behind the tiles the lane has not read yet, which is how a reset comes
+// to overrun its tile ring.
+static long g_neighbour_votes = 0;
+static inline bool hc_wave_any(bool p) {
+    if (p || g_neighbour_votes <= 0) return p;
+    --g_neighbour_votes;
+    return true;
+}
+#define M3_HOST_WAVE_ANY(p) hc_wave_any(p)
 #include "../../element-crush-gym_amd/csrc/m3_rules.hpp"
 
 #include <stdlib.h>
@@ -230,6 +243,47 @@ static void init_scalar_n(long n, const uint32_t* seeds, int8_t* out, int32_t* d
     }
 }
 
+// init_board_tiles alone, one lane, draws capped at kcap (the env prefetch's deferral boundary,
+// RESET_KCAP in k_init<CF, false>): ok[i] = what it returned; a reset it gave up (past kcap, or its
+// unread tiles would overrun the ring) is redone on FullMT only with `fallback`, else left zero.
+// neighbour: 64-draw chunks a busier lane of the same wave makes this one generate ahead (above).
+// tm / pos are exactly the ring's size, so the sanitizer build sees any index past it.
+template <class CF>
+static int tiles_n(long n, const uint32_t* seeds, uint32_t kcap, int fallback, int neighbour, int8_t* out,
+                   int32_t* draws, uint8_t* okv) {
+    using C9B = Cfg<CF::R, CF::C, CF::T>;  // (same planes; CF may only differ in its TileGen)
+    const auto dm = make_dim<C9B>();
+    int gave_up = 0;
+    for (long i = 0; i < n; ++i) {
+        typename CF::Bd P[CF::NP];
+        uint32_t tm[CF::BITS * TileGen<CF>::TWMAX], pos[TileGen<CF>::MAXR];
+        memset(tm, 0, sizeof(tm));
+        memset(pos, 0, sizeof(pos));
+        ChainMT cm;
+        cm.init(seeds[i], mt_state397(seeds[i]));
+        uint32_t d = 0;
+        g_neighbour_votes = neighbour;
+        const bool ok = init_board_tiles<CF>(P, cm, tm, pos, 1, d, 0u, [](uint32_t, uint32_t) {},
+                                             [](uint32_t, uint32_t) {}, (NoStore*)nullptr, kcap);
+        g_neighbour_votes = 0;
+        okv[i] = (uint8_t)ok;
+        draws[i] = ok ? (int32_t)d : 0;
+        if (!ok) {
+            gave_up++;
+            for (int p = 0; p < CF::NP; ++p) P[p] = CF::Bd::zero();
+            if (fallback) {
+                FullMT* fm = new FullMT;
+                fm->init(seeds[i], 0);
+                { NoStore ns; init_board<C9B>(P, *fm, ns, dm); }
+                draws[i] = (int32_t)fm->k;
+                delete fm;
+            }
+        }
+        store_planes<C9B>(P, out + i * dm.cells(), dm);
+    }
+    return gave_up;
+}
+
 template <class CF>
 static void legal_n(long n, const int8_t* boards, uint32_t* out) {
     const auto dm = make_dim<CF>();
@@ -361,6 +415,20 @@ static void rollout_n(long n, const int8_t* boards, const uint32_t* seeds, const
 
 using C9 = Cfg<9, 9, 6>;
 using C16 = Cfg<16, 16, 8>;
+// 9x9x6 on a 7-word tile ring: 32 * (7 - W - 1) = 96 usable tiles, where the shipped 10 words give
+// 192. Most single-lane resets then overrun the ring (a round's 81 tiles plus what the 64-draw chunk
+// behind them accepted), so init_board_tiles' ring_full exit -- unreachable at test sizes with the
+// shipped ring -- runs here, next to resets that complete on the small ring.
+struct C9Ring7 : C9 {};
+namespace m3 {
+template <>
+struct TileGen<C9Ring7> {
+    static constexpr int TWMAX = 7;
+    static constexpr int MAXR = TileGen<C9>::MAXR;
+    static_assert(TWMAX > C9::W + 1, "a round's read window fits the ring");
+    static M3_HD uint32_t slot(uint32_t q) { return q % (uint32_t)TWMAX; }
+};
+}  // namespace m3
 // HC_NO_WIDE=1: no 32 x 32-frame instantiations (the MemorySanitizer build: with them its -O0
 // compile needs ~40 GB and most of an hour)
 #ifndef HC_NO_WIDE
@@ -430,6 +498,18 @@ int hc_init(int cfg, long n, const uint32_t* s, int8_t* o, int32_t* d, uint32_t*
     DISPATCH(cfg, CALL);
 #undef CALL
     return rc;
+}
+// 9x9x6 init_board_tiles with the draw cap of the caller's choice and no fallback behind it:
+// ok[i] = its return value, board and draws only where ok (zero elsewhere). Returns the resets given up.
+int hc_init9_kcap(long n, const uint32_t* s, uint32_t kcap, int neighbour, int8_t* o, int32_t* d, uint8_t* ok) {
+    if (kcap > 624u || neighbour < 0) return -1;
+    return tiles_n<C9>(n, s, kcap, 0, neighbour, o, d, ok);
+}
+// 9x9x6 resets on the 7-word ring (C9Ring7), the given-up ones redone exactly (FullMT) as the
+// kernels do; ok[i] = init_board_tiles' own return value. Returns the resets that fell back.
+int hc_init9_ring7(long n, const uint32_t* s, int neighbour, int8_t* o, int32_t* d, uint8_t* ok) {
+    if (neighbour < 0) return -1;
+    return tiles_n<C9Ring7>(n, s, 624u, 1, neighbour, o, d, ok);
 }
 int hc_init_scalar(int cfg, long n, const uint32_t* s, int8_t* o, int32_t* d) {
 #define CALL(CF) init_scalar_n<CF>(n, s, o, d)

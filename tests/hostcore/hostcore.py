@@ -135,6 +135,26 @@ class HostCore:
                          _p(draws), _p(flags))
         return dict(gain=gain, steps=steps, draws=draws, flags=flags)
 
+    def _init9(self, fn, seeds, *mid):
+        assert self.cfg == 0, "the 9x9x6 tile-stream reset"
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
+        n = len(seeds)
+        out = np.zeros((n, self.N), np.int8); drw = np.zeros(n, np.int32); ok = np.zeros(n, np.uint8)
+        self.recomputed = fn(ctypes.c_long(n), _p(seeds), *mid, _p(out), _p(drw), _p(ok))
+        assert self.recomputed >= 0
+        return out, drw, ok.astype(bool)
+
+    def init_kcap(self, seeds, kcap, neighbour=0):
+        """init_board_tiles (one lane) capped at kcap draws, nothing behind it: (boards, draws, ok);
+        board and draws are zero where it gave the reset up. self.recomputed = resets given up.
+        neighbour: 64-draw chunks that a busier lane of the wave makes this one generate ahead."""
+        return self._init9(lib().hc_init9_kcap, seeds, ctypes.c_uint32(kcap), ctypes.c_int(neighbour))
+
+    def init_ring7(self, seeds, neighbour=0):
+        """The reset on a 7-word tile ring (96 usable tiles) with the exact fallback behind it:
+        (boards, draws, ok), ok = init_board_tiles finished on the ring. self.recomputed = fallbacks."""
+        return self._init9(lib().hc_init9_ring7, seeds, ctypes.c_int(neighbour))
+
     def init_scalar(self, seeds):
         seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
         n = len(seeds)

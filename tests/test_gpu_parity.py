@@ -182,7 +182,8 @@ def test_c3_1m_boards_properties():
 def test_autoreset_matches_fresh_episodes(tag):
     """After autoreset, a board continues with seed + stride exactly like a fresh episode.
     (5-move episodes: the second episode's cells come from fill_next_slots' explicit reset; the
-    prefetch path of later episodes is test_autoreset_prefetched_episodes_16x16x8.)"""
+    prefetch path of later episodes is test_autoreset_prefetched_episodes, both shapes, and
+    test_autoreset_staggered_trace_vs_oracle.)"""
     n = 2048
     env = BatchedMatch3Env(n, *SHAPES[tag], num_moves=5, env_goal=BIG, seed_base=100, autoreset=True, seed_stride=n)
     for _ in range(5):
@@ -205,21 +206,43 @@ def test_autoreset_matches_fresh_episodes(tag):
     env.close()
 
 
-def test_autoreset_prefetched_episodes_16x16x8():
-    """The step's own prefetch resets, checked on their output: with one-move episodes
-    every step autoresets every board, so steps 4.. swap in episodes that the two-stage 16x16x8 reset
-    (k_reset_stream + k_reset_tiles, the rare sixth-round boards deferred to k_init_coop) built
-    during the run. After each of 10 steps the boards, first actions and seeds must equal an
-    explicit reset of seed_base + b + k * n (k_init_fix_lane), and a sample the oracle's
-    BoardV2.__init__ (boardv2.py:17-27). 8,192 boards: ~33 per episode need the sixth round."""
-    n, base = 8192, 100
-    shape = (16, 16, 8)
+RESET_KCAP_9 = 454  # k_init<CF, false> gives up a prefetched 9x9x6 reset past this many draws (m3_kernels.hpp)
+NSLOT = 4           # episode slots per board (m3_kernels.hpp): a freed slot takes the episode NSLOT - 1 ahead
+
+
+@pytest.mark.parametrize("tag", list(SHAPES))
+def test_autoreset_prefetched_episodes(tag):
+    """The step's own prefetch resets, checked on their output: with one-move
+    episodes every step autoresets every board, so steps NSLOT.. swap in episodes that the prefetch
+    built during the run -- 9x9x6: k_init<CF, false> (stops at 454 draws, 10-word tile ring; what it
+    gives up goes to k_init_coop); 16x16x8: the two-stage reset (k_reset_stream + k_reset_tiles, the
+    rare sixth-round boards deferred to k_init_coop). Step k plays the single move of episode k - 1
+    (seeds seed_base + b + (k - 1) * n) and swaps in episode k. At each of 10 steps:
+    - the action played, the step's reward and its draw count are the oracle's for that episode (the
+      reset's stored RNG word mt[397] feeds both), and every board is done;
+    - seeds, boards and first actions equal an explicit reset of episode k's seeds (k_init_fix_lane /
+      k_init<CF, true>), and the boards the oracle's BoardV2.__init__ (boardv2.py:17-27) -- every
+      board at 9x9x6, where the explicit reset shares init_board_tiles with the prefetch, a sample
+      at 16x16x8 (8,192 boards: ~33 per episode need the sixth round);
+    - moves and scores are 0 and no reset stopped at its round cap.
+    Counters (env.stats(), since construction): every step queues n resets; at 9x9x6 the resets
+    handed to k_init_coop are bounded from the oracle's draw counts alone (see below)."""
+    n, base, steps = 8192, 100, 10
+    shape = SHAPES[tag]
+    small = tag == "9x9x6"
     env = BatchedMatch3Env(n, *shape, num_moves=1, env_goal=BIG, seed_base=base, autoreset=True, seed_stride=n)
+    st0 = env.stats()
     ctx = _native.Context(*shape)
     o = Oracle(*shape)
     pick = np.random.RandomState(5).choice(n, 48, replace=False)
-    for k in range(1, 11):
+    init_draws = {}  # episode -> the oracle's draw count of each board's reset
+    for k in range(1, steps + 1):
+        played = np.arange(base + (k - 1) * n, base + k * n, dtype=np.uint32)
+        ep = o.batch_episodes(played, 1)
+        assert (env.next_actions() == ep["actions"][:, 0]).all(), f"step {k}: action of episode {k - 1}"
         env.step()
+        assert (env.rewards() == ep["rewards"][:, 0]).all(), f"step {k}: rewards"
+        assert (env.draws() == ep["draws"][:, 0]).all(), f"step {k}: draws"
         assert env.dones().all()
         seeds = np.arange(base + k * n, base + (k + 1) * n, dtype=np.uint32)
         assert (env.seeds() == seeds).all(), f"step {k}: seeds"
@@ -230,11 +253,112 @@ def test_autoreset_prefetched_episodes_16x16x8():
         assert (env.next_actions() == want_first).all(), f"step {k}: first actions"
         assert (env.moves() == 0).all() and (env.scores() == 0).all()
         assert not (env.flags() & _native.FLAG_RESET_CAP).any()
-        for i in pick[(k - 1) * 4:k * 4 + 4]:
-            ob, _ = o.init_board(int(seeds[i]))
+        init_draws[k] = np.zeros(n, np.int64)
+        for i in (range(n) if small else pick[(k - 1) * 4:k * 4 + 4]):
+            ob, init_draws[k][i] = o.init_board(int(seeds[i]))
             assert (ob == obs[i]).all(), f"step {k}: board {i} vs the oracle"
+    st = {key: env.stats()[key] - st0[key] for key in ("autoresets", "reset_recomputes")}
+    assert st["autoresets"] == steps * n, st
+    if small:
+        # Step k frees one slot per board and queues it for episode k + NSLOT - 1 (env_fin_queue); the
+        # prefetch launch behind every step is the only one that carries the counters (the explicit
+        # resets of fill_next_slots pass none). k_init<CF, false> hands a reset to k_init_coop, which
+        # counts it, when it needs more than RESET_KCAP draws or its lane's unread tiles would
+        # overrun the ring. The first is exact from the oracle; which resets overrun depends on the
+        # lanes a reset shares its wave with, and the queue order is not deterministic. A reset of
+        # exactly 454 draws finishes in k_init on its own lane, but may overrun: it sits between
+        # the bounds. Allowance for overruns: 0.5 % (a host emulation of the wave-lockstep
+        # generator saw none in 160,000 resets).
+        for e in range(steps + 1, steps + NSLOT):  # (episodes NSLOT..steps were reset above)
+            init_draws[e] = np.array([o.init_board(base + e * n + b)[1] for b in range(n)])
+        d = np.concatenate([init_draws[e] for e in range(NSLOT, NSLOT + steps)])
+        assert len(d) == steps * n
+        lo, hi = int((d > RESET_KCAP_9).sum()), int((d >= RESET_KCAP_9).sum()) + 0.005 * len(d)
+        print(f"reset_recomputes {st['reset_recomputes']}: bounds [{lo}, {hi:.1f}] of {len(d)} queued resets")
+        assert lo <= st["reset_recomputes"] <= hi, (lo, st, hi)
     ctx.close()
     env.close()
+
+
+@pytest.mark.parametrize("tag", list(SHAPES))
+def test_autoreset_staggered_trace_vs_oracle(tag):
+    """Every step of a run whose boards reset at different times, against the oracle: 3-move
+    episodes with env_goal 20 end after 1, 2 or 3 moves (each length holds >= 5 % of the episodes: the
+    precondition below, from the oracle alone), so in 30 steps a board plays 10..30 episodes, the
+    prefetch queues of a step are partial and the slot byte wraps several times, on two shards.
+    The expected trace is walked on the host from Oracle.batch_episodes of every (board, episode)
+    seed seed_base + b + e * n. Each step: the action taken, reward, draws, done, truncated, then
+    score, moves and seed (a finished board shows the next episode's: same-step autoreset), and the
+    board of every board that reset against the oracle's BoardV2.__init__. After the last step the
+    replay check of the benchmark runs over every board."""
+    import sys
+
+    from conftest import ROOT
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    shape = SHAPES[tag]
+    n = 4096 if tag == "9x9x6" else 2048
+    base, moves, goal, steps = 100, 3, 20, 30
+    o = Oracle(*shape, episode_shuffle_cap=1024)
+    eps = [o.batch_episodes(np.arange(base + e * n, base + (e + 1) * n, dtype=np.uint32), moves, goal)
+           for e in range(steps)]
+    A, R, D = (np.stack([ep[k] for ep in eps]) for k in ("actions", "rewards", "draws"))  # [episode, board, move]
+    L = np.stack([ep["moves"] for ep in eps])                                          # [episode, board]
+    assert not (np.stack([ep["flags"] for ep in eps]) & FLAG_SHUFFLE_CAP).any()
+    share = np.bincount(L.reshape(-1), minlength=moves + 1) / L.size
+    assert share[0] == 0 and (share[1:] >= 0.05).all(), share
+    env = BatchedMatch3Env(n, *shape, num_moves=moves, env_goal=goal, seed_base=base, autoreset=True,
+                           seed_stride=n, shards=2)
+    b = np.arange(n)
+    e = np.zeros(n, np.int64)       # the episode each board is in
+    m = np.zeros(n, np.int64)       # moves it has taken in it
+    score = np.zeros(n, np.int64)
+    for t in range(steps):
+        assert (env.next_actions() == A[e, b, m]).all(), f"step {t}: actions"
+        env.step()
+        r = R[e, b, m]
+        score += r
+        tr = score >= goal
+        dn = tr | (m + 1 == moves)
+        assert (dn == (m + 1 == L[e, b])).all()  # (the oracle's own episode length)
+        assert (env.rewards() == r).all(), f"step {t}: rewards"
+        assert (env.draws() == D[e, b, m]).all(), f"step {t}: draws"
+        assert (env.dones() == dn).all(), f"step {t}: dones"
+        assert (env.truncateds() == tr).all(), f"step {t}: truncateds"
+        e, m, score = e + dn, np.where(dn, 0, m + 1), np.where(dn, 0, score)
+        seeds = (base + b + e * n).astype(np.uint32)
+        assert (env.scores() == score).all(), f"step {t}: scores"
+        assert (env.moves() == m).all(), f"step {t}: moves"
+        assert (env.seeds() == seeds).all(), f"step {t}: seeds"
+        assert not (env.flags() & _native.FLAG_RESET_CAP).any()
+        obs = env.observations()
+        for i in np.flatnonzero(dn):
+            assert (o.init_board(int(seeds[i]))[0] == obs[i]).all(), f"step {t}: board {i} after its reset"
+    assert e.min() >= steps // moves and e.max() > e.min() + 4, (e.min(), e.max())  # the resets staggered
+    chk = bench.oracle_sample_check(env, shape, moves, goal, base, n, steps, idx=np.arange(n))
+    assert chk["mismatches"] == 0 and chk["boards"] == n, chk
+    env.close()
+
+
+def test_env_reset_right_after_create_keeps_its_seeds(ctxs):
+    """A fresh env reset at once with explicit seeds holds those seeds and their boards. (Found by
+    test_determinism_and_checksum failing once: m3_env_create zeroed the per-board fields with
+    hipMemset on the null stream, which the non-blocking context stream does not wait for, so the
+    fill of the seeds could land after m3_env_reset's seed upload and the env's first boards played
+    seed 0's episode.) A race, so several envs of two sizes, each created on memory the last one
+    freed; the first action and board also against a stateless reset of the same seeds."""
+    ctx = ctxs["9x9x6"]
+    for rep in range(4):
+        for n in (20000, 200000):
+            seeds = (np.arange(n, dtype=np.uint32) * np.uint32(2654435761) + np.uint32(rep + 1)).astype(np.uint32)
+            env = BatchedMatch3Env(n, num_moves=20, env_goal=BIG, seeds=seeds, autoreset=False)
+            got_seeds, got_first, got_obs = env.seeds(), env.next_actions(), env.observations()
+            env.close()
+            assert (got_seeds == seeds).all(), (rep, n, np.flatnonzero(got_seeds != seeds)[:5])
+            want, _, first = ctx.init_boards(seeds)
+            assert (got_first == first).all() and (got_obs == want).all(), (rep, n)
 
 
 def test_determinism_and_checksum():

@@ -174,6 +174,115 @@ def test_chain_init_fallback_counts(golden):
         assert hc.recomputed == int((ini["draws_" + tag] > 623).sum())
 
 
+@pytest.fixture(scope="module")
+def oracle_resets_9x9x6():
+    """BoardV2.__init__ of seeds 100..8291 by the oracle: (seeds, boards [n, 81], draws)."""
+    o = Oracle(9, 9, 6)
+    seeds = np.arange(100, 100 + 8192, dtype=np.uint32)
+    res = [o.init_board(int(s)) for s in seeds]
+    boards = np.array([b.reshape(-1) for b, _ in res], np.int8)
+    draws = np.array([d for _, d in res], np.int64)
+    for a in (seeds, boards, draws):
+        a.setflags(write=False)
+    return seeds, boards, draws
+
+
+KCAPS = [200, 454, 455, 623, 624]
+
+
+def test_reset_draw_counts_reach_every_kcap(oracle_resets_9x9x6):
+    """Precondition of test_reset_tiles_deferral_boundary, from the oracle alone: the seed range
+    holds a reset of exactly kcap draws for every kcap under test, and resets on both sides of it.
+    (Every value is reachable: a reset takes 81 accepted draws a round, 6 in 8 draws accepted.)"""
+    _, _, draws = oracle_resets_9x9x6
+    for kcap in KCAPS:
+        assert (draws == kcap).any(), kcap
+        assert (draws > kcap).any() and (draws < kcap).any(), kcap
+
+
+@pytest.mark.parametrize("kcap", KCAPS)
+def test_reset_tiles_deferral_boundary(oracle_resets_9x9x6, kcap):
+    """init_board_tiles with a draw cap below the MT block -- the env prefetch's k_init<CF, false>
+    runs it with RESET_KCAP = 454 and defers what it gives up to k_init_coop; the harness's hc.init
+    only ever passes 624. It must finish exactly the resets whose BoardV2.__init__ (boardv2.py:17-27)
+    consumes at most kcap raw draws -- a reset of exactly kcap draws still fits -- and give up every
+    other one, and a finished reset's board and draw count are the oracle's. One lane never overruns
+    the shipped 192-tile ring (the precondition below), so the cap is the only reason to give up."""
+    seeds, boards, draws = oracle_resets_9x9x6
+    hc = HostCore(9, 9, 6)
+    out, drw, ok = hc.init_kcap(seeds, kcap)
+    want_ok = draws <= kcap
+    bad = np.flatnonzero(ok != want_ok)
+    assert not len(bad), (kcap, len(bad), seeds[bad][:5], draws[bad][:5])
+    assert hc.recomputed == int((~want_ok).sum())
+    assert (drw[ok] == draws[ok]).all()
+    assert (out[ok] == boards[ok]).all()
+    assert not out[~ok].any() and not drw[~ok].any()  # nothing half-built is handed back
+
+
+def test_reset_small_ring_overrun_falls_back_exactly(golden, oracle_resets_9x9x6):
+    """The ring_full exit of init_board_tiles: with the shipped 10-word ring (192 usable tiles) no
+    reset of a test-sized batch overruns, so the branch runs nowhere else. On a 7-word ring (96
+    usable tiles: a round's 81 plus 15) most single-lane resets overrun and must stop there -- a
+    lane that wrote on would overwrite unread tiles and hand back a wrong board with ok set. Both
+    branches must run (>= 25 % of 4,096 resets fell back, >= 10 % finished on the ring), no reset
+    that reported ok may differ from the oracle, and with the exact fallback behind it every board
+    and draw count equals the scalar reset, the oracle and the golden init fixture."""
+    hc = HostCore(9, 9, 6)
+    seeds, boards, draws = oracle_resets_9x9x6
+    seeds, boards, draws = seeds[:4096], boards[:4096], draws[:4096]
+    out, drw, ok = hc.init_ring7(seeds)
+    fell = hc.recomputed
+    assert fell == int((~ok).sum())
+    assert fell >= 0.25 * len(seeds), fell
+    assert ok.sum() >= 0.10 * len(seeds), int(ok.sum())
+    assert (draws[ok] <= 624).all()          # the cap still holds on the small ring
+    assert (~ok[draws > 624]).all()
+    assert (~ok & (draws <= 624)).sum() > 0.2 * len(seeds)  # overruns, not the draw cap, are the fallbacks
+    bad = np.flatnonzero((out != boards).any(1) | (drw != draws))
+    assert not len(bad), (len(bad), int(ok[bad].sum()), seeds[bad][:5])
+    sb, sd = hc.init_scalar(seeds)
+    assert (out == sb).all() and (drw == sd).all()
+    ini = golden("init")
+    out, drw, ok = hc.init_ring7(ini["seeds_9x9x6"].astype(np.uint32))
+    assert (out == ini["boards_9x9x6"].reshape(len(out), -1)).all() and (drw == ini["draws_9x9x6"]).all()
+    assert 0 < ok.sum() < len(ok)
+    # the shipped ring on the same seeds: one lane never overruns it (only the draw cap gives up)
+    _, _, ok10 = hc.init_kcap(seeds, 624)
+    assert (ok10 == (draws <= 624)).all()
+
+
+@pytest.mark.parametrize("ring", ["ring10", "ring7"])
+@pytest.mark.parametrize("neighbour", [1, 2, 3, 16])
+def test_reset_ring_overrun_behind_a_busy_neighbour(oracle_resets_9x9x6, ring, neighbour):
+    """What makes a reset overrun its ring on the GPU is a neighbour: the wave draws in lockstep, so
+    a lane that has the tiles of its round keeps appending 64-draw chunks for as long as another
+    lane of the wave still needs some. One lane alone never holds more than a round's 81 tiles plus
+    one chunk's (<= 145 unread), which even the 7-word ring (224 tiles of storage, 96 usable) holds
+    -- there the ring_full exit only ever fires inside its safety margin. So the harness stands in
+    for the neighbour: it keeps the wave drawing for `neighbour` more chunks (wave_any on the host,
+    tests/hostcore). From 3 chunks on the unread tiles would pass the 7-word ring's storage, from 4-5
+    on the shipped 10-word ring's (320): a lane that then wrote on would overwrite tiles it has not
+    read and hand back a wrong board with ok set. Asserted: every reset that reports ok has the
+    oracle's board and draw count; overruns happen (resets within the draw cap were given up) and,
+    behind any neighbour, some resets still finish on the ring."""
+    seeds, boards, draws = oracle_resets_9x9x6
+    seeds, boards, draws = seeds[:4096], boards[:4096], draws[:4096]
+    hc = HostCore(9, 9, 6)
+    if ring == "ring10":
+        out, drw, ok = hc.init_kcap(seeds, 624, neighbour)
+    else:
+        out, drw, ok = hc.init_ring7(seeds, neighbour)
+        assert (out == boards).all() and (drw == draws).all()  # (with the exact fallback behind it)
+    assert (draws[ok] <= 624).all()
+    bad = np.flatnonzero(ok & ((out != boards).any(1) | (drw != draws)))
+    assert not len(bad), (len(bad), seeds[bad][:5])
+    gave_up_early = int((~ok & (draws <= 624)).sum())
+    if ring == "ring7" or neighbour >= 2:
+        assert gave_up_early > 40, gave_up_early     # the overrun exit ran
+    assert ok.sum() > 40, int(ok.sum())              # and so did the ring path behind a neighbour
+
+
 def _check_steps(hc, g, tag, small):
     ok = g["terminates_" + tag] if "terminates_" + tag in g else np.ones(len(g["seed_" + tag]), bool)
     na = g["n_actions_" + tag] if "n_actions_" + tag in g else 20
