@@ -726,11 +726,13 @@ int m3_env_create(m3_ctx* c, int64_t n, int num_moves, int env_goal, m3_env** ou
     // non-blocking context and shard streams do not wait for: a fill could land after m3_env_reset's
     // seed upload on the context stream, and the first boards of the env then reset from seed 0.
     {
+        // (the counters too: m3_env_stats of an env that was loaded with m3_env_set and has not stepped
+        // yet -- rederive zeroes them at its first step -- read back whatever the allocation held)
         void* zp[] = {e->boards[0], e->boards[1], e->seeds, e->flags, e->draws, e->legal, e->score, e->moves,
-                      e->next_action, e->reward, e->done, e->trunc, e->slot};
+                      e->next_action, e->reward, e->done, e->trunc, e->slot, e->counters};
         size_t zb[] = {bytes, bytes, n * 4ull, n * 4ull, n * 4ull, n * 4ull * c->AW, n * 4ull, n * 4ull,
-                       n * 4ull, n * 4ull, (size_t)n, (size_t)n, (size_t)n};
-        for (int i = 0; i < 13 && err == hipSuccess; ++i) err = hipMemsetAsync(zp[i], 0, zb[i], c->stream);
+                       n * 4ull, n * 4ull, (size_t)n, (size_t)n, (size_t)n, 64 * 4 * (size_t)MAX_SHARDS};
+        for (int i = 0; i < 14 && err == hipSuccess; ++i) err = hipMemsetAsync(zp[i], 0, zb[i], c->stream);
         if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
     }
     if (err != hipSuccess) {

@@ -151,6 +151,41 @@ class Oracle:
                                    ctypes.byref(mt), ctypes.byref(flags), self.shuffle_cap)
         return out, int(r), int(mt.draws), int(flags.value)
 
+    def random_action(self, board, seed):
+        """np.random.seed(seed); np.random.choice(legal_actions(board)) -- an episode's first action
+        (samplerTasks.py:11-13) and a rollout's (mcts.py:17): (action, draws), (-1, 0) without a
+        legal move."""
+        board = np.ascontiguousarray(board, dtype=np.int32)
+        legal = np.zeros(self.A, dtype=np.int32)
+        nl = lib().m3o_legal_actions(ctypes.byref(self.cfg), _p(board, ctypes.c_int32), _p(legal, ctypes.c_int32))
+        if not nl:
+            return -1, 0
+        mt = MT()
+        lib().m3o_mt_seed(ctypes.byref(mt), seed & 0xFFFFFFFF)
+        a = int(legal[lib().m3o_randint(ctypes.byref(mt), 0, nl)])
+        return a, int(mt.draws)
+
+    def apply_action_next(self, board, seed, action, n_actions=20):
+        """apply_action plus the seeded random action that follows it (samplerTasks.py:13, as
+        m3o_random_episode draws it): legal[randint(0, len(legal))] from the stream where
+        apply_action left it. Returns (next_board, reward, draws, flags, next_action, draws_after);
+        next_action is -1 and nothing is drawn when the step did not run or left no legal move."""
+        board = np.ascontiguousarray(board, dtype=np.int32)
+        out = np.zeros_like(board)
+        mt = MT()
+        flags = ctypes.c_int()
+        r = lib().m3o_apply_action(ctypes.byref(self.cfg), seed & 0xFFFFFFFF, int(n_actions),
+                                   _p(board, ctypes.c_int32), int(action), _p(out, ctypes.c_int32),
+                                   ctypes.byref(mt), ctypes.byref(flags), self.shuffle_cap)
+        draws, nxt, after = int(mt.draws), -1, int(mt.draws)
+        if not flags.value & (FLAG_TERMINAL | FLAG_BAD_ACTION):
+            legal = np.zeros(self.A, dtype=np.int32)
+            nl = lib().m3o_legal_actions(ctypes.byref(self.cfg), _p(out, ctypes.c_int32), _p(legal, ctypes.c_int32))
+            if nl:
+                nxt = int(legal[lib().m3o_randint(ctypes.byref(mt), 0, nl)])
+                after = int(mt.draws)
+        return out, int(r), draws, int(flags.value), nxt, after
+
     def random_episode(self, seed, num_moves=20, env_goal=2**31 - 1):
         acts = np.zeros(num_moves, np.int32)
         rews = np.zeros(num_moves, np.int32)

@@ -359,7 +359,8 @@ static void rounds_n(long n, const int8_t* boards, const uint32_t* seeds, const 
 // MCTS.rollout (mctslib/standard/mcts.py:14-19) the way k_rollout's rollout_one runs it: the first
 // choice on the rollout seed's chain, every step and later choice on the step seed's chain. Writes
 // gain, steps, draws (global-stream position when the rollout ends), flags; -1 gain when the chain
-// ran out (the kernel's k_rollout_fix replay).
+// ran out (the kernel's k_rollout_fix replay). The group table is the full one (ArrayStore), so a
+// board with many groups (tests/crafted.py) is played here and not given up.
 template <class CF>
 static void rollout_n(long n, const int8_t* boards, const uint32_t* seeds, const int32_t* nact, const uint32_t* rseeds,
                       int32_t* gain, int32_t* steps, uint32_t* draws, uint32_t* flags) {
@@ -370,7 +371,7 @@ static void rollout_n(long n, const int8_t* boards, const uint32_t* seeds, const
         ChainMT first, rng;
         first.init(rseeds[i], mt_state397(rseeds[i]));
         rng.init(seeds[i], mt_state397(seeds[i]));
-        SmallStore<CF, 6> st;
+        ArrayStore<CF> st;
         int nn = nact[i], g = 0, s = 0;
         uint32_t fl = 0u, dr = 0u;
         bool ok = true;
