@@ -714,8 +714,6 @@ int m3_env_create(m3_ctx* c, int64_t n, int num_moves, int env_goal, m3_env** ou
         constexpr size_t RW = CONT_REC<decltype(cf)>;
         if constexpr (K::CASCADE_LIMIT >= 0) alloc(&e->cont, RW * n * 4ull);
         if constexpr (RESET_TWO_STAGE<decltype(cf)>) alloc(&e->tab, (size_t)TwoStage<decltype(cf)>::TW * n * 4ull);
-        if constexpr (RESET_TWO_STAGE_REJ<decltype(cf)>)
-            alloc(&e->tab, (size_t)TwoStageRej<decltype(cf)>::TW * n * 4ull);
         return 0;
     });
     for (hipEvent_t& ev : e->gev)
@@ -766,15 +764,8 @@ int m3_env_set_shards(m3_env* e, int nshards) {
         m3_env::Shard sh;
         sh.off = std::min<int64_t>(e->n, s * per);
         sh.n = std::min<int64_t>(e->n, sh.off + per) - sh.off;
-        if (M3_STREAM_PRIO) {  // the step stream first at dispatch, the prefetch resets last
-            int least = 0, greatest = 0;
-            HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-            HIP_TRY(hipStreamCreateWithPriority(&sh.stream, hipStreamNonBlocking, greatest));
-            HIP_TRY(hipStreamCreateWithPriority(&sh.pstream, hipStreamNonBlocking, least));
-        } else {
-            HIP_TRY(hipStreamCreateWithFlags(&sh.stream, hipStreamNonBlocking));
-            HIP_TRY(hipStreamCreateWithFlags(&sh.pstream, hipStreamNonBlocking));
-        }
+        HIP_TRY(hipStreamCreateWithFlags(&sh.stream, hipStreamNonBlocking));
+        HIP_TRY(hipStreamCreateWithFlags(&sh.pstream, hipStreamNonBlocking));
         HIP_TRY(hipEventCreateWithFlags(&sh.ev, hipEventDisableTiming));
         for (hipEvent_t& ev : sh.pev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         for (hipEvent_t& ev : sh.aev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));

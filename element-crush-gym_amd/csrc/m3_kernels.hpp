@@ -53,17 +53,19 @@ constexpr int FIX_GRID = 16;       // step fixup almost never has work: few bloc
 constexpr int INIT_FIX_BLOCK = 64;
 constexpr int INIT_BLOCK = 64;
 // active lanes of the one-board-per-lane fix / reset kernels (KS::BPW: one for the 32 x 32 frame)
-// (M3_WIDE_FRAME_LANES: an experiment knob, 64 to run the 32 x 32 frame one board per LANE again)
-#ifndef M3_WIDE_FRAME_LANES
-#define M3_WIDE_FRAME_LANES 1
-#endif
 template <class CF>
-constexpr uint32_t lanes_for() { return CF::W > 8 ? (uint32_t)M3_WIDE_FRAME_LANES : 64u; }
+constexpr uint32_t lanes_for() { return CF::W > 8 ? 1u : 64u; }
 // 9x9: k_init redoes its few > 624-draw resets in-wave (wave_reset); 16x16
 // resets go straight to k_init_fix_lane (most need >= 624 draws)
 template <class CF>
 constexpr bool INIT_INLINE_FIX = CF::N <= 128;
 constexpr int MAX_SHARDS = 8;  // env board shards (one HIP stream each)
+// The M3_* macros of the device sources are of three kinds only: numeric tunings that `make variant
+// XFLAGS=-D...` varies (the #ifndef-guarded numbers, from here on and M3_TW9 / M3_LEGAL_SLICED_W in
+// m3_rules.hpp), M3_FAST_MATCH (m3_rules.hpp: the host test compares both sides), and build structure
+// / diagnostic builds (M3_SPLIT_TU, M3_INST, M3_PART, M3_HEADLINE_ONLY, M3_NO_WIDE_FRAME;
+// M3_PHASE_PROF, M3_TEST_NO_GATHER_WAIT, M3_DEBUG_NO_PREFETCH). On/off switches of variants that were
+// measured and rejected are not kept: DESIGN.md has their numbers, git history their code.
 // k_init's lockstep draw budget when it may defer (env prefetch): 9x9x6 resets
 // past 454 draws (~4 %: the third chain level and the second block) go to
 // k_init_coop, so a wave no longer runs to its slowest lane's ~600 draws
@@ -71,7 +73,6 @@ constexpr int MAX_SHARDS = 8;  // env board shards (one HIP stream each)
 #define M3_RESET_KCAP 454
 #endif
 constexpr uint32_t RESET_KCAP = M3_RESET_KCAP;
-// grid caps of the env-prefetch reset kernels (0: sized by the queue's usual length), see launch_init
 // The prefetch reset launches are sized for n / PF_DIV queued resets of the shard (grid-strided beyond
 // that; blocks past the queue's length exit at once). Round 6: every board's episode ends on the same
 // step (the bench's 20-move episodes all start together), so one step in 20 queues the whole shard;
@@ -86,17 +87,6 @@ constexpr uint32_t RESET_KCAP = M3_RESET_KCAP;
 #endif
 #ifndef M3_COOP_GMAX  // most blocks of a prefetch k_init_coop launch (one deferred reset per wave at a time)
 #define M3_COOP_GMAX 4096
-#endif
-#ifndef M3_PF_GRID
-#define M3_PF_GRID 0
-#endif
-#ifndef M3_PF_COOP_GRID
-#define M3_PF_COOP_GRID 0
-#endif
-// 16x16x8 resets: 1 = lane-per-board on the two-block register chain (k_init_chain2),
-// 0 = lane-per-board FullMT in scratch (k_init_fix_lane)
-#ifndef M3_RESET16_CHAIN2
-#define M3_RESET16_CHAIN2 0
 #endif
 // A reset stops after this many rounds of BoardV2.__init__'s redraw loop (boardv2.py:23-27) and
 // flags M3_FLAG_RESET_CAP: only two-colour boards get near it (a 16x16x2 reset can need more than
@@ -120,7 +110,7 @@ struct KS {
     // ~2,500 SGPR spills through VGPR lanes, and with several lanes active some boards came out
     // wrong only in company (32x32x8 steps: 92 of 689; each exact alone) -- the lane interference
     // DESIGN.md §4 describes for the 16 x 16 frame. One active lane per wave has no divergence.
-    static constexpr int BPW = CF::W > 8 ? M3_WIDE_FRAME_LANES : B;
+    static constexpr int BPW = CF::W > 8 ? 1 : B;
 #ifndef M3_STEP_WPS
 #define M3_STEP_WPS 4
 #endif
@@ -157,15 +147,6 @@ struct KS {
     // the 3-waves/SIMD bound shifts with it.
     using Chain = std::conditional_t<(CF::N > 128), ChainMT1, ChainMT>;
     using Rng = Chain;
-// Issue priorities against the prefetch resets that share the SIMDs (A/B knobs, off by default):
-// M3_STEP_PRIO -- s_setprio of the k_env_step waves; M3_STREAM_PRIO -- the shard's step stream at
-// the device's greatest stream priority and its prefetch stream at the least.
-#ifndef M3_STEP_PRIO
-#define M3_STEP_PRIO 0
-#endif
-#ifndef M3_STREAM_PRIO
-#define M3_STREAM_PRIO 0
-#endif
 #ifndef M3_CASCADE_LIMIT
 #define M3_CASCADE_LIMIT 2
 #endif
@@ -335,20 +316,10 @@ __device__ __forceinline__ void prof_drain(S&) {
 
 // Staging barrier of the one-wave (64-lane) workgroups: it only has to order
 // this wave's own LDS accesses (a wave's DS instructions execute in issue
-// order), so a wavefront-scope fence suffices. __syncthreads() would also make
-// the wave wait for every global store it has in flight (vmcnt(0) of the
-// workgroup-scope release), i.e. a full memory round trip per kernel tail.
-#ifndef M3_WAVE_SYNC
-#define M3_WAVE_SYNC 0
-#endif
-__device__ __forceinline__ void lds_sync() {
-#if M3_WAVE_SYNC
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-#else
-    __syncthreads();
-#endif
-}
+// order). __syncthreads() also makes the wave wait for every global store it
+// has in flight (vmcnt(0) of the workgroup-scope release); a wavefront-scope
+// fence + wave barrier in its place measured equal and was removed.
+__device__ __forceinline__ void lds_sync() { __syncthreads(); }
 
 // ---------------------------------------------------------------------------
 // LDS staging
@@ -641,9 +612,6 @@ constexpr int PF_LAG = NSLOT - 1;   // steps between a prefetch and its first us
 // per shard-step and no cross-block ticket.
 constexpr int CBLOCKS = PF_LAG + 1;
 static_assert(8 * CBLOCKS <= 40, "the counter blocks end where a shard's stats begin (m3_env::counters, word 40)");
-#ifndef M3_STAGE_PAD  // k_env_step's 16x16 staging rows 16 B apart (bank conflicts, see block_copy_in_rows)
-#define M3_STAGE_PAD 1
-#endif
 
 // A reset launch processes "items". Item i is (board b, seed, slot): with a
 // list (env prefetch) b = list[i], seed = list_seed[i], slot = list_slot[i];
@@ -1087,93 +1055,6 @@ __global__ void __launch_bounds__(INIT_FIX_BLOCK) k_init_fix_lane(InitArgs a) {
     }
 }
 
-// One round of randint(1, T+1, (R, C)) for a power-of-two T (every draw is a
-// tile) as a rolled loop over the board's words: the RNG code appears once in
-// the kernel instead of once per unrolled word (fill_round), which keeps a
-// large generator such as ChainMT2 from multiplying the register peak.
-template <class CF, class RNG>
-__device__ __forceinline__ void fill_round_seq(typename CF::Bd* P, RNG& mt, const typename CF::Bd* only) {
-    static_assert(CF::TILE_RNG != 0u && CF::TILE_RNG == CF::TILE_MASK && CF::N % 32 == 0, "N draws per round");
-    constexpr int BITS = CF::BITS;
-#pragma unroll 1
-    for (int w = 0; w < CF::W; ++w) {
-        uint32_t t[BITS];
-#pragma unroll
-        for (int p = 0; p < BITS; ++p) t[p] = 0u;
-#pragma unroll 1
-        for (int bit = 0; bit < 32; ++bit) {
-            const uint32_t v = (mt.next32() & CF::TILE_MASK) + 1u;
-#pragma unroll
-            for (int p = 0; p < BITS; ++p) t[p] |= ((v >> p) & 1u) << bit;
-        }
-        const uint32_t m = only ? only->word_at(w) : 0xFFFFFFFFu;
-#pragma unroll
-        for (int p = 0; p < BITS; ++p) {
-#pragma unroll
-            for (int i = 0; i < CF::W; ++i)
-                if (i == w) P[p].w[i] = (P[p].w[i] & ~m) | (t[p] & m);
-        }
-    }
-}
-
-// ---- lane-per-board reset on the two-block register chain (16x16x8) -------
-// Every reset of the launch, one board per lane, on ChainMT2: the first 1248
-// raw outputs of seed(s) from registers (m3_rng.hpp), so no reset walks a
-// 2.5 KB lane-private state in scratch. With a power-of-two tile count every
-// round of randint(1, T+1, (R, C)) takes exactly R*C draws (16x16x8: 256), so
-// the lanes of a wave draw in lockstep and the chain's level changes are
-// wave-uniform. A reset that would need a round past draw 1248 (16x16x8: a
-// 5th round, ~2 % of resets) leaves the lane: appended to the defer list for
-// k_init_coop (one wave per board; every launch of this kernel carries a defer
-// list). stats[1] counts the resets the wave-cooperative pass finishes.
-template <class CF>
-__global__ void __launch_bounds__(INIT_BLOCK) k_init_chain2(InitArgs a) {
-    static_assert(!CF::DYN && INIT_BLOCK == 64, "specialised shapes, one-wave blocks");
-    constexpr bool LOCKSTEP = CF::TILE_RNG != 0u && CF::TILE_RNG == CF::TILE_MASK;  // N draws per round
-    static_assert(LOCKSTEP, "power-of-two tile counts (16x16x8)");
-    const int64_t cnt = a.list_count ? (int64_t)*a.list_count : a.n;
-    if (a.stats && blockIdx.x == 0 && threadIdx.x == 0 && cnt) atomicAdd(&a.stats[0], (uint32_t)cnt);
-    const typename CF::Dim dm{};
-    for (int64_t base = (int64_t)blockIdx.x * INIT_BLOCK; base < cnt; base += (int64_t)gridDim.x * INIT_BLOCK) {
-        const int64_t i = base + threadIdx.x;
-        bool ok = true;
-        if (i < cnt) {
-            int64_t b;
-            uint32_t seed, slot;
-            init_item(a, i, b, seed, slot);
-            const uint32_t m397 = mt_state397(seed);
-            ChainMT2 mt;
-            mt.init(seed, m397);
-            typename CF::Bd P[CF::NP], mask;
-#pragma unroll
-            for (int p = 0; p < CF::NP; ++p) P[p] = CF::Bd::zero();
-            fill_round_seq<CF>(P, mt, nullptr);                                 // boardv2.py:21
-            for (;;) {                                                          // :23-27
-                if (!get_match_mask<CF>(P, mask)) break;
-                if (mt.k + (uint32_t)CF::N > ChainMT2::LIMIT) {  // the next round leaves the chain
-                    ok = false;
-                    break;
-                }
-                fill_round_seq<CF>(P, mt, &mask);
-            }
-            if (ok) {
-                if (a.m397) a.m397[(int64_t)slot * a.cstride + b] = m397;
-                const int64_t ob = (int64_t)slot * a.sstride + b;
-                init_outputs<CF>(a, b, ob, seed, m397, mt.draws(), P, dm);
-                init_store_board<CF>(a, ob, P, dm);
-            }
-        }
-        const uint64_t bad = __ballot(!ok);
-        if (bad) {  // left to k_init_coop (one wave per board): one wave-aggregated append
-            const int lane = (int)threadIdx.x;
-            uint32_t q = 0;
-            if (lane == 0) q = atomicAdd(a.defer_count, (uint32_t)__popcll(bad));
-            q = __shfl(q, 0);
-            if (!ok) a.defer[q + (uint32_t)__popcll(bad & ((1ull << lane) - 1ull))] = (uint32_t)i;
-        }
-    }
-}
-
 // ---- two-stage reset (16x16x8 env prefetch) -----------------------------
 // Each round of BoardV2.__init__'s redraw loop draws a whole (R, C) board
 // (boardv2.py:21, :25), and with a power-of-two tile count every draw is a
@@ -1189,9 +1070,6 @@ __global__ void __launch_bounds__(INIT_BLOCK) k_init_chain2(InitArgs a) {
 // A reset that needs a round past ROUNDS (~2 %) goes to k_init_coop's defer
 // list (one wave per board, from the seed). This replaces the lane-private
 // 2.5 KB FullMT state that k_init_fix_lane walks in scratch.
-#ifndef M3_RESET16_TWO_STAGE
-#define M3_RESET16_TWO_STAGE 1
-#endif
 #ifndef M3_TS_BOARDS
 #define M3_TS_BOARDS 4
 #endif
@@ -1205,8 +1083,7 @@ template <class CF, bool DYN = CF::DYN>  // (frame configurations have no compil
 struct TwoStageOk : std::false_type {};
 template <class CF>
 struct TwoStageOk<CF, false>
-    : std::bool_constant<M3_RESET16_TWO_STAGE && (CF::N > 128) && CF::N % 64 == 0 && CF::TILE_RNG != 0u &&
-                         CF::TILE_RNG == CF::TILE_MASK> {};
+    : std::bool_constant<(CF::N > 128) && CF::N % 64 == 0 && CF::TILE_RNG != 0u && CF::TILE_RNG == CF::TILE_MASK> {};
 template <class CF>
 constexpr bool RESET_TWO_STAGE = TwoStageOk<CF>::value;
 template <class CF>
@@ -1447,8 +1324,6 @@ __global__ void __launch_bounds__(64) k_reset_tiles(InitArgs a) {
     }
 }
 
-#include "m3_reset9.hpp"
-
 // mt[397] of init_genrand(seeds[b]): the chain word of each board's current
 // episode (env resume, m3_env_set)
 __global__ void __launch_bounds__(256) k_mt397(int64_t n, const uint32_t* seeds, uint32_t* out) {
@@ -1664,7 +1539,7 @@ __device__ __forceinline__ void env_fin_store(typename CF::Bd* P, const EnvArgs&
         }
         if constexpr (EnvFin<CF>::CELLS_IN_REGS) {
             if (!cells) {
-                // (k_env_step with M3_COOP_CELLS: the wave copies them, coop_reset_cells)
+                // (k_env_step: the wave copies them, coop_reset_cells)
             } else if (row) {
                 store_cells<CF::N>(row, e.cw);
             } else {
@@ -1691,11 +1566,8 @@ __device__ __forceinline__ void env_fin_queue(const EnvArgs& a, int64_t b, uint3
 
 // The next episode's cells of the wave's resetting lanes (mask m), copied into their LDS staging
 // rows by the whole wave: NWS lanes per board, one dword each (64 / NWS boards per pass), instead of
-// NWS words in every lane's registers across the atomic (M3_COOP_CELLS). ob: the lane's slot word
+// NWS words in every lane's registers across the atomic. ob: the lane's slot word
 // offset (EnvFin::ob). Loads of every pass first, then the byte writes.
-#ifndef M3_COOP_CELLS
-#define M3_COOP_CELLS 1
-#endif
 template <class CF>
 __device__ __forceinline__ void coop_reset_cells(const EnvArgs& a, uint64_t m, int64_t ob, uint8_t* lds, int row_stride) {
     constexpr int NWS = EnvFin<CF>::NWS;
@@ -1862,10 +1734,9 @@ __global__ void __launch_bounds__(KS<CF>::B, KS<CF>::STEP_WPS) k_env_step(EnvArg
     // inside it; with one wave per workgroup nothing else can touch the LDS
     // in between, so the two share storage (9 KB per wave at 9x9: the 6-slot table).
     using K = KS<CF>;
-    if constexpr (M3_STEP_PRIO > 0) __builtin_amdgcn_s_setprio(M3_STEP_PRIO);
     static_assert(K::B == 64, "staging/table aliasing assumes one wave per workgroup");
     // 16x16: staging rows padded by 16 B (block_copy_in_rows)
-    constexpr int RPAD = (!CF::DYN && CF::N % 64 == 0 && M3_STAGE_PAD) ? 16 : 0;
+    constexpr int RPAD = (!CF::DYN && CF::N % 64 == 0) ? 16 : 0;
     constexpr int STAGE_WORDS = (K::B * (CF::N + RPAD) + 16 + 3) / 4;
     constexpr int TAB_WORDS = LdsStore<CF, K::GCAP, K::B>::WORDS;
     __shared__ __attribute__((aligned(16))) uint32_t stage_tab[STAGE_WORDS > TAB_WORDS ? STAGE_WORDS : TAB_WORDS];
@@ -1893,7 +1764,7 @@ __global__ void __launch_bounds__(KS<CF>::B, KS<CF>::STEP_WPS) k_env_step(EnvArg
     st.spill = a.spill;
     st.pool_next = &a.counters[CNT_SPILL];
     st.pool_cap = K::SPILL_RECORDS;
-    bool reset_lane = false;  // (M3_COOP_CELLS: the wave copies the resetting lanes' next cells below)
+    bool reset_lane = false;  // (the wave copies the resetting lanes' next cells below)
     int64_t reset_ob = 0;
     if (t < nb) {
         const int64_t b = b0 + t;
@@ -1932,7 +1803,7 @@ __global__ void __launch_bounds__(KS<CF>::B, KS<CF>::STEP_WPS) k_env_step(EnvArg
             EnvFin<CF> e;
             const uint32_t seed_in = rng.seed;
             if (res == ENV_STEP_DONE &&
-                !env_fin_begin<CF>(P, a, b, rng, st, r, f, HL, VL, mv, sc0, dm, row, e, &cslot, &seed_in, !M3_COOP_CELLS))
+                !env_fin_begin<CF>(P, a, b, rng, st, r, f, HL, VL, mv, sc0, dm, row, e, &cslot, &seed_in, false))
                 res = ENV_STEP_RECOMPUTE;
             const bool fin = res == ENV_STEP_DONE, paused = res == ENV_STEP_PAUSED;
             const bool reset = fin && e.reset;
@@ -1956,7 +1827,7 @@ __global__ void __launch_bounds__(KS<CF>::B, KS<CF>::STEP_WPS) k_env_step(EnvArg
             }
             prof_drain(st);
             mark<PH_TATOM>(st);
-            if (fin) env_fin_store<CF>(P, a, b, st, e, dm, row, !M3_COOP_CELLS);
+            if (fin) env_fin_store<CF>(P, a, b, st, e, dm, row, false);
             reset_lane = reset;
             reset_ob = e.ob;
             if (mp | mr) {
@@ -1976,7 +1847,7 @@ __global__ void __launch_bounds__(KS<CF>::B, KS<CF>::STEP_WPS) k_env_step(EnvArg
             if constexpr (!CF::DYN) {
                 o.slot = &cslot;
                 o.seed = &seed_in;
-                o.cells = !M3_COOP_CELLS;
+                o.cells = false;
                 o.reset = &reset_lane;
                 o.ob = &reset_ob;
             }
@@ -1987,7 +1858,7 @@ __global__ void __launch_bounds__(KS<CF>::B, KS<CF>::STEP_WPS) k_env_step(EnvArg
             }
         }
     }
-    if constexpr (M3_COOP_CELLS && !CF::DYN) {
+    if constexpr (!CF::DYN) {
         const uint64_t mr = __ballot(reset_lane);  // (all 64 lanes: a ragged last wave too)
         if (mr) coop_reset_cells<CF>(a, mr, reset_ob, lds, NC + RPAD);
     }
@@ -2041,25 +1912,13 @@ __global__ void __launch_bounds__(KS<CF>::B, KS<CF>::CONT_WPS) k_env_cont_grid(E
 // k_env_fix runs on the step stream between two steps of a shard and almost never has work
 // (16x16x8: 7 recomputed boards in 50 steps of 262,144); at 512 VGPRs (16x16x8) its waves can only
 // start on a SIMD with no other wave resident (31 us average launch duration in the trace).
-// M3_FIX_LEAN=1: the specialised shapes run it one board per wave under a 128-VGPR bound (the rare
-// recompute spills to scratch; one active lane, so no divergence under the spills). Measured OFF:
-// 16x16x8 0.74-0.75 vs 0.80 G env-steps/s, 9x9 equal (gpurun_out/r05ac) -- the launch was not
-// what held the shard's stream.
-#ifndef M3_FIX_LEAN
-#define M3_FIX_LEAN 0
-#endif
 template <class CF>
-constexpr uint32_t env_fix_lanes() { return (!CF::DYN && M3_FIX_LEAN) ? 1u : lanes_for<CF>(); }
-template <class CF>
-constexpr int ENV_FIX_WPS = (!CF::DYN && M3_FIX_LEAN) ? 4 : 1;
-
-template <class CF>
-__global__ void __launch_bounds__(FIX_BLOCK, ENV_FIX_WPS<CF>) k_env_fix(EnvArgs a) {
+__global__ void __launch_bounds__(FIX_BLOCK, 1) k_env_fix(EnvArgs a) {
     const uint32_t cnt = a.counters[CNT_OVF];
     if (blockIdx.x == 0 && threadIdx.x == 0 && cnt) atomicAdd(&a.stats[0], cnt);
     if (a.zero_next && blockIdx.x == 0 && threadIdx.x < 8) a.zero_next[threadIdx.x] = 0u;  // (CBLOCKS)
     const typename CF::Dim dm(a.shape);
-    constexpr uint32_t L = env_fix_lanes<CF>();
+    constexpr uint32_t L = lanes_for<CF>();
     for (uint32_t i = blockIdx.x * L + threadIdx.x; threadIdx.x < L && i < cnt; i += gridDim.x * L) {
         const int64_t b = a.ovf_list[i];
         typename CF::Bd P[CF::NP];
@@ -2386,43 +2245,13 @@ int launch_init(hipStream_t stream, const InitArgs& a, int64_t max_items) {
     if (max_items == 0) return M3_OK;
     int64_t g = (max_items + INIT_BLOCK - 1) / INIT_BLOCK;
     if (g > 4096) g = 4096;
-    // env prefetch (a.defer): the reset kernels grid-stride over the queue, and their waves share the
-    // CUs with the step kernels (k_init holds ~10 KB of LDS per wave, about one step wave's
-    // worth); capping their grids bounds how many run at once. The queue is needed PF_LAG steps later.
-    const int64_t pf_cap = a.defer ? (int64_t)M3_PF_GRID : 0, coop_cap = a.defer ? (int64_t)M3_PF_COOP_GRID : 0;
-    if (pf_cap > 0 && g > pf_cap) g = pf_cap;
     if constexpr (INIT_INLINE_FIX<CF>) {
-        if constexpr (RESET_TWO_STAGE_REJ<CF>) {
-            if (a.tab && a.defer) {  // 9x9x6 env prefetch (m3_reset9.hpp)
-                int64_t ga = (max_items + TwoStageRej<CF>::G - 1) / TwoStageRej<CF>::G;
-                ga = ga > 2048 ? 2048 : ga;
-                hipLaunchKernelGGL(k_reset_stream_rej<CF>, dim3((unsigned)ga), dim3(64), 0, stream, a);
-                HIP_TRY(hipGetLastError());
-                hipLaunchKernelGGL(k_reset_tiles_rej<CF>, dim3((unsigned)g), dim3(64), 0, stream, a);
-                HIP_TRY(hipGetLastError());
-                int64_t gc = max_items / 64 + 1;  // the few past the table's rounds
-                gc = gc < 64 ? 64 : (gc > 4096 ? 4096 : gc);
-                if (coop_cap > 0 && gc > coop_cap) gc = coop_cap;
-                hipLaunchKernelGGL(k_init_coop<CF>, dim3((unsigned)gc), dim3(64), 0, stream, a);
-                HIP_TRY(hipGetLastError());
-                return M3_OK;
-            }
-        }
         if (a.defer) hipLaunchKernelGGL((k_init<CF, false>), dim3((unsigned)g), dim3(INIT_BLOCK), 0, stream, a);
         else hipLaunchKernelGGL((k_init<CF, true>), dim3((unsigned)g), dim3(INIT_BLOCK), 0, stream, a);
         if (a.defer) {  // sized for the usual ~4 % deferred share, grid-strided
             HIP_TRY(hipGetLastError());
             int64_t gc = max_items / 16 + 1;
             gc = gc < 64 ? 64 : (gc > M3_COOP_GMAX ? M3_COOP_GMAX : gc);
-            if (coop_cap > 0 && gc > coop_cap) gc = coop_cap;
-            hipLaunchKernelGGL(k_init_coop<CF>, dim3((unsigned)gc), dim3(64), 0, stream, a);
-        }
-    } else if constexpr (!CF::DYN && M3_RESET16_CHAIN2) {  // 16x16x8: ~60 % of resets need the second MT block
-        hipLaunchKernelGGL(k_init_chain2<CF>, dim3((unsigned)g), dim3(INIT_BLOCK), 0, stream, a);
-        if (a.defer) {  // the ~2 % past draw 1248, one wave per board
-            HIP_TRY(hipGetLastError());
-            int64_t gc = max_items / 32 + 1;
-            gc = gc < 64 ? 64 : (gc > 4096 ? 4096 : gc);
             hipLaunchKernelGGL(k_init_coop<CF>, dim3((unsigned)gc), dim3(64), 0, stream, a);
         }
     } else if (RESET_TWO_STAGE<CF> && a.tab && a.defer) {  // 16x16x8 env prefetch (see k_reset_stream)
@@ -2430,14 +2259,12 @@ int launch_init(hipStream_t stream, const InitArgs& a, int64_t max_items) {
             const InitArgs& s = a;
             int64_t ga = (max_items + TwoStage<CF>::G - 1) / TwoStage<CF>::G;
             ga = ga > 2048 ? 2048 : ga;
-            if (pf_cap > 0 && ga > pf_cap) ga = pf_cap;
             hipLaunchKernelGGL(k_reset_stream<CF>, dim3((unsigned)ga), dim3(64), 0, stream, s);
             HIP_TRY(hipGetLastError());
             hipLaunchKernelGGL(k_reset_tiles<CF>, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(64), 0, stream, s);
             HIP_TRY(hipGetLastError());
             int64_t gc = max_items / 32 + 1;  // the ~2 % past the table's rounds
             gc = gc < 64 ? 64 : (gc > M3_COOP_GMAX ? M3_COOP_GMAX : gc);
-            if (coop_cap > 0 && gc > coop_cap) gc = coop_cap;
             hipLaunchKernelGGL(k_init_coop<CF>, dim3((unsigned)gc), dim3(64), 0, stream, a);
         }
     } else {  // frame shapes: FullMT (lane-private scratch); 32 x 32 frame: one board per wave
@@ -2469,7 +2296,6 @@ void prefetch_args(const m3_env* e, int64_t o, InitArgs& r) {
     r.slot_flags = e->ne_flags + o;
     r.cstride = e->n;
     if constexpr (RESET_TWO_STAGE<CF>) r.tab = e->tab ? e->tab + o * TwoStage<CF>::TW : nullptr;
-    if constexpr (RESET_TWO_STAGE_REJ<CF>) r.tab = e->tab ? e->tab + o * TwoStageRej<CF>::TW : nullptr;
 }
 
 // Enqueue one env step of shard s: on the step stream, wait for the prefetch
@@ -2545,8 +2371,8 @@ int launch_env_shard(m3_env* e, int s, const int32_t* d_actions) {
         hipLaunchKernelGGL(k_env_cont_grid<CF>, dim3((unsigned)(g > 0 ? g : 1)), dim3(KS<CF>::B), 0, st, a);
         HIP_TRY(hipGetLastError());
     }
-    // (one board per wave: 64 waves; else FIX_GRID x 64 lanes)
-    hipLaunchKernelGGL(k_env_fix<CF>, dim3(env_fix_lanes<CF>() == 1u ? 64 : fix_grid<CF>()), dim3(FIX_BLOCK), 0, st, a);
+    // (one board per wave, the 32 x 32 frame: 64 waves; else FIX_GRID x 64 lanes)
+    hipLaunchKernelGGL(k_env_fix<CF>, dim3(lanes_for<CF>() == 1u ? 64 : fix_grid<CF>()), dim3(FIX_BLOCK), 0, st, a);
     HIP_TRY(hipGetLastError());
     if (timed) {  // the whole step pipeline of the shard, fixup pass included
         HIP_TRY(hipEventRecord(e->tev[3 * e->tn + 2], st));
@@ -2566,7 +2392,7 @@ int launch_env_shard(m3_env* e, int s, const int32_t* d_actions) {
         r.list_slot = e->pf_slot[par] + o;
         r.list_count = &cnt[CNT_PF];
         r.stats = base + 41;
-        if constexpr (INIT_INLINE_FIX<CF> || (!CF::DYN && M3_RESET16_CHAIN2) || RESET_TWO_STAGE<CF>) {
+        if constexpr (INIT_INLINE_FIX<CF> || RESET_TWO_STAGE<CF>) {
             r.defer = e->defer + o;
             r.defer_count = &cnt[CNT_PF_DEFER];  // zeroed with the block
         }

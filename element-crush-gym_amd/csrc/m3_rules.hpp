@@ -285,13 +285,6 @@ M3_HD bool wave_any(bool p) {
 #endif
 }
 
-// The cascade loop of apply_cascade_ex with a wave-uniform exit (see there): 1 everywhere, 2 in the
-// frame configurations only (the specialised 16x16x8 step measured 9 % slower with it, 9x9 1-2 %),
-// 0 nowhere
-#ifndef M3_UNIFORM_CASCADE
-#define M3_UNIFORM_CASCADE 2
-#endif
-
 // boards of at least this many words take the word-sliced legal_masks (0: never)
 #ifndef M3_LEGAL_SLICED_W
 #define M3_LEGAL_SLICED_W 5
@@ -972,10 +965,7 @@ M3_HD void merge_clip(typename CF::Bd* P, const typename CF::Bd& z, const typena
 // of each distance is a column-wise suffix parity of the holes still counted (mp), and moving
 // the low bits first never lets two tiles meet. A stage no lane of the wave needs is skipped as
 // a whole (wave-uniform branch): the wave runs ceil(log2 R) fixed stages at most instead of the
-// row-by-row loop's max-drop + 1 passes, with no divergence (M3_GRAVITY_LOOP=1: the loop).
-#ifndef M3_GRAVITY_LOOP
-#define M3_GRAVITY_LOOP 0
-#endif
+// earlier row-by-row loop's max-drop + 1 passes, with no divergence.
 template <class CF>
 M3_HD typename CF::Bd gravity_decomp(typename CF::Bd* P, const typename CF::Dim& dm = typename CF::Dim{}) {
     using Bd = typename CF::Bd;
@@ -1018,33 +1008,12 @@ M3_HD typename CF::Bd gravity_decomp(typename CF::Bd* P, const typename CF::Dim&
     return VALID.andnot(m);
 }
 
+// (A forwarding function of its own on purpose: with the body under this name the inliner visits the
+// cascade kernels' callees in another order and their register allocation changes -- the 32 x 32 frame
+// kernels' spill counts move by hundreds of VGPRs.)
 template <class CF>
 M3_HD typename CF::Bd gravity(typename CF::Bd* P, const typename CF::Dim& dm = typename CF::Dim{}) {
-    if constexpr (!M3_GRAVITY_LOOP) return gravity_decomp<CF>(P, dm);
-    using Bd = typename CF::Bd;
-    constexpr int C = CF::C, R = CF::R, NPU = 6;
-    const Bd VALID = dm.valid();  // walls are neither holes nor tiles
-    Bd occ = P[0];
-#pragma unroll
-    for (int p = 1; p < NPU; ++p) occ |= P[p];
-    for (;;) {  // drop every tile that has a hole somewhere below it by one row
-        const Bd e = VALID.andnot(occ);
-        Bd s = at<C>(e);
-        s |= at<C>(s);
-        s |= at<2 * C>(s);
-        s |= at<4 * C>(s);
-        if constexpr (R > 9) s |= at<8 * C>(s);
-        if constexpr (R > 17) s |= at<16 * C>(s);
-        const Bd mv = occ & s;
-        if (!mv.any()) break;
-#pragma unroll
-        for (int p = 0; p < NPU; ++p) {
-            const Bd m = P[p] & mv;
-            P[p] = P[p].andnot(mv) | at<-C>(m);
-        }
-        occ = occ.andnot(mv) | at<-C>(mv);
-    }
-    return VALID.andnot(occ);
+    return gravity_decomp<CF>(P, dm);
 }
 
 // refill of the top-aligned empty cells em
@@ -1271,7 +1240,8 @@ M3_HD int apply_cascade_ex(typename CF::Bd* P, RNG& rng, uint32_t& flags, typena
         Bd mask;
         bool found = false;
         if (!settled) {
-            if constexpr (M3_UNIFORM_CASCADE == 1 || (M3_UNIFORM_CASCADE == 2 && CF::DYN)) {
+            if constexpr (CF::DYN) {
+                // (frame configurations only: the specialised 16x16x8 step measured 9 % slower with it, 9x9 1-2 %)
                 // cascade: refill, rematch, clear while matches remain -- with a wave-UNIFORM loop exit:
                 // the wave runs its longest lane's trip count (as the divergent loop does) with the
                 // body predicated per lane, so no value leaves the loop from a lane that quit early.
@@ -1520,7 +1490,10 @@ struct TileGen {
 #ifndef M3_TW9
 #define M3_TW9 10
 #endif
-    static constexpr int TWMAX = CF::N <= 128 ? M3_TW9 : 32;  // ring words per plane
+    // ring words per plane. Only the small specialised shapes (N <= 128) reset on the ring in a kernel
+    // (k_init); the 32-word arm serves the host test harness alone, which also runs init_board_tiles
+    // at 16x16x8 -- no 16x16 kernel uses the ring.
+    static constexpr int TWMAX = CF::N <= 128 ? M3_TW9 : 32;
     static constexpr int MAXR = 624 / CF::N + 2;             // rounds one MT block can feed
     static_assert(TWMAX > CF::W + 1, "a round's read window fits the ring");
     // ring slot of stream word q (a mask for a power of two, else a modulo by a constant)

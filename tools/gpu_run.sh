@@ -3,7 +3,6 @@
 #   smoke                 __graft_entry__.smoke()
 #   tests[:<pytest args>] the -m gpu suite (or the given files / -k filter), e.g. "tests:tests/test_gpu_parity.py -k prefetched"
 #   bench9 | bench16      bench.py at C3 / C4 (driver command for C3: defaults)
-#   ab:<lib>[:<args>]     parity gate (tools/gpu_ab.sh) + timing of a library variant in build/
 # Every GPU step runs under its own time limit; the first failing step ends the call.
 set -o pipefail
 export TMPDIR=/tmp

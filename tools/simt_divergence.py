@@ -113,8 +113,7 @@ int main(int argc, char** argv) {
 PATCHES = [  # (anchor, text inserted after it)
     ("    while (cand.any()) {                                       // row-major scan over run starts", "\n        SIM_TRIP(1);"),
     ("    while (trig.any()) {\n        const int x = trig.lowest();", "\n        SIM_TRIP(2);"),
-    ("    for (;;) {  // drop every tile that has a hole somewhere below it by one row", "\n        SIM_TRIP(3);"),
-    # round 5: the decomposed gravity -- a stage counts for a lane that still has holes to close
+    # the decomposed gravity -- a stage counts for a lane that still has holes to close
     ("        constexpr int D = (1 << decltype(S)::value) * C;  // rows moved in this stage, as bits",
      "\n        if (mk.any()) SIM_TRIP(3);"),
     ("        uint32_t v = rng.next32() & tmask;", "\n        SIM_TRIP(4);"),
