@@ -305,6 +305,8 @@ int m3_ctx_destroy(m3_ctx* c) {
     if (c->dbuf) (void)hipFree(c->dbuf);
     if (c->hbuf) (void)hipHostFree(c->hbuf);
     if (c->counters) (void)hipFree(c->counters);
+    for (hipEvent_t ev : c->tev)
+        if (ev) (void)hipEventDestroy(ev);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return M3_OK;
@@ -546,6 +548,109 @@ int m3_legal_actions(m3_ctx* c, int64_t n, const int8_t* boards, uint32_t* out_l
     });
     if (rc) return rc;
     return stage_download(c, out, {out_legal_bits}, dout);
+}
+
+// ---- one-ply lookahead --------------------------------------------------------
+constexpr int LOOK_OVF_WORD = 12;  // c->counters[12]: the lookahead's exact-pass count (zeroed per call)
+
+// a.n, the inputs and the outputs set; the exact pass's list comes from `list` ([n] words of device memory)
+static int enqueue_lookahead(m3_ctx* c, LookArgs a, uint32_t* list) {
+    a.shape = c->sdesc;
+    a.ovf_count = c->counters + LOOK_OVF_WORD;
+    a.ovf_list = list;
+    HIP_TRY(hipMemsetAsync(a.ovf_count, 0, 4, c->stream));
+    return with_shape(c->shape, [&](auto cf) { return launch_lookahead<decltype(cf)>(c->stream, a); });
+}
+
+int m3_lookahead_device(m3_ctx* c, int64_t n, const int8_t* boards, const uint32_t* seeds, const int32_t* n_actions,
+                        int32_t* out_best_action, int32_t* out_best_reward, int32_t* out_values,
+                        uint32_t* out_last_draws, uint32_t* out_flags) {
+    CHECK_ARG(c && n >= 0, "bad arguments");
+    if (n == 0) return M3_OK;
+    CHECK_ARG(n < (int64_t)1 << 31, "n too large");
+    CHECK_ARG(boards && seeds && n_actions, "null buffer");
+    int rc = check_ids_on_board(c);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    rc = ensure_scratch(c, n * 4ull + 256);
+    if (rc) return rc;
+    LookArgs a{};
+    a.n = n;
+    a.boards = boards;
+    a.seeds = seeds;
+    a.n_actions = n_actions;
+    a.best_action = out_best_action;
+    a.best_reward = out_best_reward;
+    a.values = out_values;
+    a.last_draws = out_last_draws;
+    a.flags = out_flags;
+    return enqueue_lookahead(c, a, (uint32_t*)c->dbuf);
+}
+
+int m3_lookahead(m3_ctx* c, int64_t n, const int8_t* boards, const uint32_t* seeds, const int32_t* n_actions,
+                 int32_t* out_best_action, int32_t* out_best_reward, int32_t* out_values, uint32_t* out_last_draws,
+                 uint32_t* out_flags) {
+    CHECK_ARG(c && n >= 0, "bad arguments");
+    if (n == 0) return M3_OK;
+    CHECK_ARG(n < (int64_t)1 << 31, "n too large");
+    CHECK_ARG(boards && seeds && n_actions, "null buffer");
+    int rc = check_ids_on_board(c);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t bytes = n * (size_t)c->N, vbytes = out_values ? n * 4ull * c->A : 0;
+    const bool zc = n <= ZC_MAX_BOARDS;  // zero-copy: the kernels read and write the pinned buffer
+    Image in, out;
+    Image& im_out = zc ? in : out;  // (zero-copy: one image holds both)
+    const int i_b = in.add(bytes), i_s = in.add(n * 4ull), i_na = in.add(n * 4ull);
+    const int o_bad = im_out.add(16), o_a = im_out.add(out_best_action ? n * 4ull : 0),
+              o_r = im_out.add(out_best_reward ? n * 4ull : 0), o_v = im_out.add(vbytes),
+              o_d = im_out.add(out_last_draws ? n * 4ull : 0), o_f = im_out.add(out_flags ? n * 4ull : 0);
+    char *din, *dout, *hout;
+    uint32_t* list;
+    if (zc) {
+        rc = ensure_host(c, in.total + 256);
+        if (rc) return rc;
+        rc = ensure_scratch(c, n * 4ull + 256);
+        if (rc) return rc;
+        char* h = (char*)c->hbuf;
+        memcpy(h + in.off[i_b], boards, bytes);
+        memcpy(h + in.off[i_s], seeds, n * 4);
+        memcpy(h + in.off[i_na], n_actions, n * 4);
+        memset(h + in.off[o_bad], 0, 16);
+        din = dout = (char*)c->hdev;
+        hout = h;
+        list = (uint32_t*)c->dbuf;
+    } else {
+        rc = stage_begin(c, in, out, n * 4ull, &din);
+        if (rc) return rc;
+        dout = din + ((in.total + 255) & ~size_t(255));
+        list = (uint32_t*)(dout + ((out.total + 255) & ~size_t(255)));
+        rc = stage_upload(c, in, {boards, seeds, n_actions}, din, 16);  // (zeroes the bad-cell word)
+        if (rc) return rc;
+        hout = (char*)c->hbuf;
+    }
+    LookArgs a{};
+    a.n = n;
+    a.boards = (const int8_t*)(din + in.off[i_b]);
+    a.seeds = (const uint32_t*)(din + in.off[i_s]);
+    a.n_actions = (const int32_t*)(din + in.off[i_na]);
+    a.bad_cells = (uint32_t*)(dout + im_out.off[o_bad]);
+    a.best_action = out_best_action ? (int32_t*)(dout + im_out.off[o_a]) : nullptr;
+    a.best_reward = out_best_reward ? (int32_t*)(dout + im_out.off[o_r]) : nullptr;
+    a.values = out_values ? (int32_t*)(dout + im_out.off[o_v]) : nullptr;
+    a.last_draws = out_last_draws ? (uint32_t*)(dout + im_out.off[o_d]) : nullptr;
+    a.flags = out_flags ? (uint32_t*)(dout + im_out.off[o_f]) : nullptr;
+    rc = enqueue_lookahead(c, a, list);
+    if (rc) return rc;
+    if (!zc) HIP_TRY(hipMemcpyAsync(hout, dout, out.total, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (*(volatile uint32_t*)(hout + im_out.off[o_bad])) return bad_cells_error();
+    if (out_best_action) memcpy(out_best_action, hout + im_out.off[o_a], n * 4);
+    if (out_best_reward) memcpy(out_best_reward, hout + im_out.off[o_r], n * 4);
+    if (out_values) memcpy(out_values, hout + im_out.off[o_v], vbytes);
+    if (out_last_draws) memcpy(out_last_draws, hout + im_out.off[o_d], n * 4);
+    if (out_flags) memcpy(out_flags, hout + im_out.off[o_f], n * 4);
+    return M3_OK;
 }
 
 // ---- rollouts ---------------------------------------------------------------
@@ -798,7 +903,7 @@ int m3_env_destroy(m3_env* e) {
                     e->next_action, e->reward, e->done, e->trunc, e->actions[0], e->actions[1], e->counters,
                     e->ovf_list,
                     e->packed, e->gathered, e->slot, e->ne_words, e->ne_first, e->ne_legal, e->ne_flags,
-                    e->spill, e->m397, e->cont, e->defer, e->tab};
+                    e->spill, e->m397, e->cont, e->defer, e->tab, e->look_act, e->look_list, e->look_cnt};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (int q = 0; q < PF_LAG; ++q)
@@ -926,6 +1031,59 @@ int m3_env_step(m3_env* e, const int32_t* actions) {
     const int rc = m3_env_step_device(e, e->actions[pb]);
     e->upload_this = false;
     return rc;
+}
+
+// The lookahead of the env's current boards, per shard on the shard's step stream: behind the
+// previous step's k_env_step / k_env_cont_grid / k_env_fix, ahead of whatever is enqueued next.
+int m3_env_lookahead(m3_env* e, int32_t* d_best_action, int32_t* d_best_reward, int32_t* d_values) {
+    CHECK_ARG(e, "null env");
+    if (!e->ready)
+        return set_err(M3_ERR_STATE, "m3_env_lookahead before m3_env_reset (or before m3_env_set of boards, seeds, "
+                                     "score, moves and next_action)");
+    m3_ctx* c = e->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = ensure_fresh(e);
+    if (rc) return rc;
+    if (!e->look_list) {
+        HIP_TRY(hipMalloc(&e->look_list, e->n * 4));
+        HIP_TRY(hipMalloc(&e->look_cnt, MAX_SHARDS * 4));
+    }
+    for (int s = 0; s < (int)e->shards.size(); ++s) {
+        m3_env::Shard& sh = e->shards[s];
+        if (sh.n == 0) continue;
+        const int64_t o = sh.off;
+        LookArgs a{};
+        a.shape = c->sdesc;
+        a.n = sh.n;
+        a.boards = e->boards[e->cur] + o * c->N;
+        a.seeds = e->seeds + o;
+        a.moves = e->moves + o;
+        a.num_moves = e->num_moves;
+        a.best_action = d_best_action ? d_best_action + o : nullptr;
+        a.best_reward = d_best_reward ? d_best_reward + o : nullptr;
+        a.values = d_values ? d_values + o * c->A : nullptr;
+        a.ovf_count = e->look_cnt + s;
+        a.ovf_list = e->look_list + o;
+        HIP_TRY(hipMemsetAsync(a.ovf_count, 0, 4, sh.stream));
+        rc = with_shape(c->shape, [&](auto cf) { return launch_lookahead<decltype(cf)>(sh.stream, a); });
+        if (rc) return rc;
+        HIP_TRY(hipEventRecord(sh.ev, sh.stream));  // (the shard's last work: m3_env_get joins on it)
+    }
+    return M3_OK;
+}
+
+int m3_env_step_greedy(m3_env* e) {
+    CHECK_ARG(e, "null env");
+    if (!e->ready)
+        return set_err(M3_ERR_STATE, "m3_env_step_greedy before m3_env_reset (or before m3_env_set of boards, "
+                                     "seeds, score, moves and next_action)");
+    HIP_TRY(hipSetDevice(e->ctx->device));
+    if (!e->look_act) HIP_TRY(hipMalloc(&e->look_act, e->n * 4));
+    // (each shard's step kernel follows its lookahead on the same stream, and the lookahead of the
+    // next step follows the step: look_act needs no double buffer)
+    int rc = m3_env_lookahead(e, e->look_act, nullptr, nullptr);
+    if (rc) return rc;
+    return m3_env_step_device(e, e->look_act);
 }
 
 static int env_field(m3_env* e, int what, void** ptr, size_t* bytes) {
@@ -1167,6 +1325,20 @@ int m3_prof_read(uint64_t* out, int reset) {
 int m3_prof_read(uint64_t* out, int reset) { return m3_prof_read_tu(out, reset); }
 #endif
 #endif
+
+// Device time of whatever is enqueued on the context stream between the two marks.
+int m3_ctx_timer(m3_ctx* c, int what, float* out_ms) {
+    CHECK_ARG(c && what >= 0 && what <= 1 && (what == 0 || out_ms), "bad arguments");
+    HIP_TRY(hipSetDevice(c->device));
+    for (hipEvent_t& ev : c->tev)
+        if (!ev) HIP_TRY(hipEventCreate(&ev));
+    HIP_TRY(hipEventRecord(c->tev[what], c->stream));
+    if (what == 1) {
+        HIP_TRY(hipEventSynchronize(c->tev[1]));
+        HIP_TRY(hipEventElapsedTime(out_ms, c->tev[0], c->tev[1]));
+    }
+    return M3_OK;
+}
 
 int m3_env_timing(m3_env* e, int capacity) {
     CHECK_ARG(e && capacity >= 0, "bad arguments");

@@ -30,6 +30,7 @@ template int launch_apply<CF_PART>(m3_ctx*, const ApplyArgs&);
 template int launch_legal<CF_PART>(m3_ctx*, int64_t, const int8_t*, uint32_t*);
 template int fill_next_slots<CF_PART>(m3_env*);
 template int rederive<CF_PART>(m3_env*);
+template int launch_lookahead<CF_PART>(hipStream_t, const LookArgs&);
 #elif M3_PART == 3
 template int launch_rollouts<CF_PART>(m3_ctx*, const RolloutArgs&);
 #else

@@ -2130,6 +2130,7 @@ struct m3_ctx {
     void* hdev = nullptr;  // hbuf as the device addresses it (zero-copy calls)
     size_t hcap = 0;
     uint32_t* counters = nullptr;  // rollouts: [0] overflow count, [1] spill records, [2] bad-cell waves
+    hipEvent_t tev[2] = {nullptr, nullptr};  // m3_ctx_timer: start / stop on the context stream (created on first use)
 };
 
 struct m3_env {
@@ -2183,6 +2184,11 @@ struct m3_env {
     int64_t steps = 0;
     int32_t* packed = nullptr;
     int32_t* gathered = nullptr;
+    // one-ply lookahead (m3_env_lookahead / m3_env_step_greedy), allocated on first use: the greedy
+    // actions [n], the exact pass's board list [n] and its count per shard
+    int32_t* look_act = nullptr;
+    uint32_t* look_list = nullptr;
+    uint32_t* look_cnt = nullptr;
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;
     // per-step kernel timing ring (bench.py roofline): event pair i brackets
@@ -2486,6 +2492,9 @@ int launch_rollouts(m3_ctx* c, const RolloutArgs& a) {
     KW int launch_env_step<CF>(m3_env*, const int32_t*);                           \
     KW int fill_next_slots<CF>(m3_env*);                                           \
     KW int rederive<CF>(m3_env*);                                                  \
-    KW int launch_rollouts<CF>(m3_ctx*, const RolloutArgs&);
+    KW int launch_rollouts<CF>(m3_ctx*, const RolloutArgs&);                       \
+    KW int launch_lookahead<CF>(hipStream_t, const LookArgs&);
 
 }  // namespace m3k
+
+#include "m3_lookahead.hpp"  // k_lookahead, k_lookahead_fix, launch_lookahead

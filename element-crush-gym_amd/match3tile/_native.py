@@ -35,11 +35,12 @@ EXPORTS = [
     "m3_abi_version", "m3_last_error", "m3_device_count", "m3_supported", "m3_action_space",
     "m3_ctx_create", "m3_ctx_destroy", "m3_ctx_synchronize", "m3_dev_alloc", "m3_dev_free", "m3_dev_copy",
     "m3_init_boards", "m3_init_boards_ex", "m3_apply_actions", "m3_legal_actions", "m3_rollouts", "m3_rollouts_device",
+    "m3_lookahead", "m3_lookahead_device", "m3_env_lookahead", "m3_env_step_greedy",
     "m3_env_create", "m3_env_destroy", "m3_env_reset", "m3_env_set_shards", "m3_env_synchronize",
     "m3_env_set_autoreset", "m3_env_step",
     "m3_env_step_device", "m3_env_get", "m3_env_set", "m3_env_device_ptr",
     "m3_comm_unique_id", "m3_env_comm_init", "m3_env_comm_size", "m3_env_gather", "m3_env_gather_device", "m3_env_debug_stall",
-    "m3_env_stats", "m3_env_timing",
+    "m3_env_stats", "m3_ctx_timer", "m3_env_timing",
     "m3_env_kernel_ms", "m3_env_step_kernel_ms",
 ]
 
@@ -85,6 +86,10 @@ def lib():
             "m3_legal_actions": ([vp, i64, vp, vp], i32),
             "m3_rollouts": ([vp, i64] + [vp] * 9, i32),
             "m3_rollouts_device": ([vp, i64] + [vp] * 9, i32),
+            "m3_lookahead": ([vp, i64] + [vp] * 8, i32),
+            "m3_lookahead_device": ([vp, i64] + [vp] * 8, i32),
+            "m3_env_lookahead": ([vp, vp, vp, vp], i32),
+            "m3_env_step_greedy": ([vp], i32),
             "m3_env_create": ([vp, i64, i32, i32, vp], i32),
             "m3_env_destroy": ([vp], i32),
             "m3_env_reset": ([vp, vp, u32], i32),
@@ -103,6 +108,7 @@ def lib():
             "m3_env_gather_device": ([vp, vp], i32),
             "m3_env_debug_stall": ([vp, u32], i32),
             "m3_env_stats": ([vp, vp], i32),
+            "m3_ctx_timer": ([vp, i32, vp], i32),
             "m3_env_timing": ([vp, i32], i32),
             "m3_env_kernel_ms": ([vp, vp, i32, vp], i32),
             "m3_env_step_kernel_ms": ([vp, vp, i32, vp], i32),
@@ -274,6 +280,30 @@ class Context:
         res = dict(gain=gain, steps=steps, draws=draws, flags=flags)
         if final_boards:
             res["final"] = fin.reshape(n, self.rows, self.columns)
+        return res
+
+    def lookahead(self, boards, seeds, n_actions, values=False):
+        """One-ply lookahead (BoardV2.greedy_action, boardv2.py:209-218) of n states in one launch: the
+        step reward of every legal action, evaluated on the device.
+
+        Returns best_action (lowest id among the maxima, -1 without a legal action), best_reward,
+        last_draws (draws of the highest legal id's apply: where the reference's loop leaves numpy's
+        global stream), flags and, with values=True, the [n, A] table (-1 where illegal)."""
+        b = self._boards(boards)
+        n = len(b)
+        seeds = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint32), (n,)))
+        na = np.ascontiguousarray(np.broadcast_to(np.asarray(n_actions, dtype=np.int32), (n,)))
+        best = np.empty(n, np.int32)
+        rew = np.empty(n, np.int32)
+        draws = np.empty(n, np.uint32)
+        flags = np.empty(n, np.uint32)
+        tab = np.empty((n, self.A), np.int32) if values else None
+        with self._lock:
+            check(lib().m3_lookahead(self.handle, n, ptr(b), ptr(seeds), ptr(na), ptr(best), ptr(rew), ptr(tab),
+                                     ptr(draws), ptr(flags)))
+        res = dict(best_action=best, best_reward=rew, last_draws=draws, flags=flags)
+        if values:
+            res["values"] = tab
         return res
 
     def legal_actions(self, board):

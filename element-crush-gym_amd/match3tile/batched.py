@@ -98,6 +98,35 @@ class BatchedMatch3Env:
     def step_device(self, device_actions_ptr=None):
         check(lib().m3_env_step_device(self.handle, device_actions_ptr))
 
+    def step_greedy(self):
+        """One env step with every board playing BoardV2.greedy_action (boardv2.py:209-218): the
+        device lookahead of the current boards, then the step on its picks -- nothing leaves HBM."""
+        check(lib().m3_env_step_greedy(self.handle))
+
+    def lookahead_device(self, best_action_ptr=None, best_reward_ptr=None, values_ptr=None):
+        """Enqueue the one-ply lookahead of the current boards into caller-owned device buffers
+        (int32[n], int32[n], int32[n][A]; None skips one); valid after synchronize() or for any later
+        call on the env."""
+        check(lib().m3_env_lookahead(self.handle, best_action_ptr, best_reward_ptr, values_ptr))
+
+    def lookahead(self, values: bool = False) -> dict:
+        """Host copies of the one-ply lookahead of the current boards: best_action (-1 without a legal
+        action), best_reward and, with values=True, the [n, A] step-reward table (-1 where illegal)."""
+        bufs = [self.ctx.device_empty(4 * self.n), self.ctx.device_empty(4 * self.n),
+                self.ctx.device_empty(4 * self.n * self.A) if values else None]
+        try:
+            self.lookahead_device(bufs[0].ptr, bufs[1].ptr, bufs[2].ptr if values else None)
+            self.synchronize()
+            res = dict(best_action=bufs[0].to_host(np.int32, (self.n,)),
+                       best_reward=bufs[1].to_host(np.int32, (self.n,)))
+            if values:
+                res["values"] = bufs[2].to_host(np.int32, (self.n, self.A))
+        finally:
+            for b in bufs:
+                if b is not None:
+                    b.free()
+        return res
+
     def synchronize(self):
         check(lib().m3_env_synchronize(self.handle))
 

@@ -6,6 +6,10 @@ reference functions take no arguments and draw the board seed from numpy's
 global RNG (``BoardConfig()``, boardConfig.py:34); here ``seed`` may be given
 to make an episode reproducible, and ``None`` keeps the reference behaviour.
 
+``greedy_actions_device(states)`` is the same list from ONE ``m3_lookahead`` call: the states go up
+once (no host legal sets, no board per candidate) and the device evaluates every legal action;
+``greedy_episodes(seeds)`` plays whole greedy episodes in one batched env.
+
 ``greedy_actions(states)`` is ``[s.greedy_action for s in states]``
 (boardv2.py:209-218) for many boards in ONE launch: every legal action of
 every state is applied by one ``m3_apply_actions`` call and each state keeps
@@ -19,7 +23,7 @@ import numpy as np
 
 from . import _native
 from .boardConfig import BoardConfig
-from .boardv2 import BoardV2, _sync_global_rng
+from .boardv2 import BoardV2, _ids_past_board, _sync_global_rng
 from .mcts import MCTS
 
 
@@ -88,3 +92,41 @@ def greedy_actions(states: Sequence[BoardV2], sync_rng: bool = False) -> List:
     if sync_rng and counts[-1] and not states[-1].is_terminal:
         _sync_global_rng(states[-1].cfg.seed, int(res["draws"][-1]))
     return out
+
+
+def greedy_actions_device(states: Sequence[BoardV2], sync_rng: bool = False) -> List:
+    """``greedy_actions`` over the device lookahead (m3_lookahead): one board per state goes up,
+    the legal sets and every candidate stay on the device. Same contract: None for a state without
+    a legal action; sync_rng=True leaves numpy's global RNG as the LAST state's greedy_action would."""
+    states = list(states)
+    if not states:
+        return []
+    cfg = states[0].cfg
+    shape = (cfg.rows, cfg.columns, cfg.types)
+    if any((s.cfg.rows, s.cfg.columns, s.cfg.types) != shape for s in states):
+        raise ValueError("greedy_actions_device() needs states of one board shape")
+    _ids_past_board(cfg)  # rows < columns: IndexError, as legal_actions / apply_action raise
+    boards = np.stack([np.asarray(s.array) for s in states])
+    seeds = np.array([int(s.cfg.seed) & 0xFFFFFFFF for s in states], dtype=np.uint32)
+    n_act = np.array([s.n_actions for s in states], dtype=np.int32)
+    res = _native.context(*shape).lookahead(boards, seeds, n_act)
+    out = [None if a < 0 else int(a) for a in res["best_action"]]
+    if sync_rng and out[-1] is not None and not states[-1].is_terminal:
+        _sync_global_rng(states[-1].cfg.seed, int(res["last_draws"][-1]))
+    return out
+
+
+def greedy_episodes(seeds, moves: int = 20, rows: int = 9, columns: int = 9, types: int = 6, device: int = 0):
+    """``greedy_test`` (samplerTasks.py:17-22) for every seed at once: one batched env, autoreset off
+    and no score goal, ``moves`` greedy steps on the device. Returns the episode scores [len(seeds)]."""
+    from .batched import BatchedMatch3Env
+
+    seeds = np.ascontiguousarray(np.atleast_1d(seeds), dtype=np.uint32)
+    env = BatchedMatch3Env(len(seeds), rows, columns, types, num_moves=moves, env_goal=2**31 - 1, device=device,
+                           seeds=seeds, autoreset=False)
+    try:
+        for _ in range(moves):
+            env.step_greedy()
+        return env.scores().astype(np.int64)
+    finally:
+        env.close()

@@ -123,6 +123,31 @@ int m3_rollouts_device(m3_ctx *ctx, int64_t n, const int8_t *boards, const uint3
                        const int32_t *n_actions, const uint32_t *rollout_seeds, int32_t *out_gain,
                        int32_t *out_steps, uint32_t *out_draws, uint32_t *out_flags, int8_t *out_boards);
 
+/* ---- one-ply lookahead (BoardV2.greedy_action, boardv2.py:209-218) ------ */
+
+/* For n independent states (board, cfg.seed, n_actions): the step reward of EVERY legal action,
+ * i.e. apply_action(a).reward - state.reward for each a of legal_actions (boardv2.py:209-218,
+ * samplers.greedy_actions), each on a private copy of the board with the stream reseeded from
+ * cfg.seed, the dead-board shuffle and everything after it included.
+ *   out_values [n][A]  the step reward of action a if legal, -1 otherwise
+ *   out_best_action    the lowest legal id among the maxima (the reference's loop keeps the first
+ *                      strict maximum of the ascending legal list); -1 without a legal action
+ *   out_best_reward    that reward; -1 without a legal action
+ *   out_last_draws     raw draws of the apply of the HIGHEST legal id -- where numpy's global
+ *                      stream stands after the reference's loop; 0 if terminal or none legal
+ *   out_flags          OR of the candidates' M3_FLAG_*, M3_FLAG_NO_LEGAL without a legal action,
+ *                      M3_FLAG_TERMINAL for n_actions < 1 (every legal action is then worth 0)
+ * Every out is nullable. Host buffers; blocks until done. Cells outside [0, 127]: M3_ERR_INVALID.
+ * Boards with a side above 16 (the 32 x 32 frame): M3_ERR_UNSUPPORTED. */
+int m3_lookahead(m3_ctx *ctx, int64_t n, const int8_t *boards, const uint32_t *seeds,
+                 const int32_t *n_actions, int32_t *out_best_action, int32_t *out_best_reward,
+                 int32_t *out_values, uint32_t *out_last_draws, uint32_t *out_flags);
+/* Same on device buffers, enqueued on the context stream (no sync). Inputs must stay valid until
+ * the stream reaches the launch. */
+int m3_lookahead_device(m3_ctx *ctx, int64_t n, const int8_t *boards, const uint32_t *seeds,
+                        const int32_t *n_actions, int32_t *out_best_action, int32_t *out_best_reward,
+                        int32_t *out_values, uint32_t *out_last_draws, uint32_t *out_flags);
+
 /* ---- device-resident batched env: n x Match3Env (env.py:8-65) ----------- */
 
 /* num_moves / env_goal as Match3Env(num_moves=20, env_goal=500) (env.py:15-16). */
@@ -156,6 +181,17 @@ int m3_env_set_autoreset(m3_env *env, int enabled, uint32_t seed_stride);
 int m3_env_step(m3_env *env, const int32_t *actions);
 /* Same with actions already in device memory (int32[n]); NULL = random. */
 int m3_env_step_device(m3_env *env, const int32_t *d_actions);
+
+/* The one-ply lookahead (m3_lookahead, boardv2.py:209-218) of the env's CURRENT boards, with their
+ * current episode seeds and n_actions = num_moves - moves taken, as the next step would apply them.
+ * Device buffers int32[n], int32[n], int32[n][A], each nullable. Enqueued per shard on the shard's
+ * step stream, behind the previous step: the results are valid after m3_env_synchronize, or for
+ * any later call on the env. M3_ERR_STATE before m3_env_reset. */
+int m3_env_lookahead(m3_env *env, int32_t *d_best_action, int32_t *d_best_reward, int32_t *d_values);
+/* Match3Env.step with every board playing BoardV2.greedy_action (boardv2.py:209-218, the policy of
+ * samplerTasks.greedy_test): m3_env_lookahead into a buffer of the env, then m3_env_step_device on
+ * it. A board without a legal action plays -1, as under the random policy (M3_FLAG_BAD_ACTION). */
+int m3_env_step_greedy(m3_env *env);
 
 /* What to copy out. */
 #define M3_ENV_BOARDS 0      /* int8  [n][rows*columns]  observation (env.py:56) */
@@ -230,6 +266,10 @@ int m3_env_stats(m3_env *env, uint64_t out[4]);
  * k_env_fix). m3_env_kernel_ms waits for them and returns the per-launch
  * durations of the whole pipeline in ms (out_n of them); m3_env_step_kernel_ms
  * the same for k_env_step alone (the dominant kernel, bench.py's roofline). */
+/* Stopwatch on the context stream (HIP events): what = 0 marks the start; what = 1 marks the stop,
+ * waits for it and returns in *out_ms the device time of everything enqueued on the context stream
+ * between the two marks (the *_device calls; tools/lookahead_bench.py). */
+int m3_ctx_timer(m3_ctx *ctx, int what, float *out_ms);
 int m3_env_timing(m3_env *env, int capacity);
 int m3_env_kernel_ms(m3_env *env, float *out_ms, int max_n, int *out_n);
 int m3_env_step_kernel_ms(m3_env *env, float *out_ms, int max_n, int *out_n);

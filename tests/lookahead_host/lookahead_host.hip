@@ -1,0 +1,212 @@
+// TEST-ONLY host build of the one-ply lookahead core (element-crush-gym_amd/csrc/m3_lookahead_core.hpp):
+// the same M3_HD functions k_lookahead and k_lookahead_fix call -- candidate enumeration (prefix
+// search, k-th set bit), the packed key, one candidate's apply_action, the per-board fold and the
+// hand-over to the exact pass -- driven by a serial emulation of a wave: groups of `bpw` boards,
+// rounds of 64 candidates, lane after lane. Not part of the product.
+//
+// cfg 0 = Cfg<9,9,6>, cfg 1 = Cfg<16,16,8>, cfg 2 = the 16 x 16 frame for the shape set by
+// lh_set_frame (the lookahead is not built for the 32 x 32 frame).
+#include "../../element-crush-gym_amd/csrc/m3_lookahead_core.hpp"
+
+#include <stdlib.h>
+#include <string.h>
+
+#include <vector>
+
+using namespace m3;
+
+static int g_T = 6;
+static Shape g_shape = make_shape(9, 9, 6);
+
+// KS<CF>::GCAP and KS<CF>::Chain of m3_kernels.hpp (the test holds lh_gcap / lh_chain_limit to
+// tests/crafted.py, which test_crafted_cpu pins to the source)
+template <class CF>
+struct HK {
+    static constexpr int GCAP = CF::N <= 128 ? 6 : 4;
+    using Chain = std::conditional_t<(CF::N > 128), ChainMT1, ChainMT>;
+    static constexpr int LIMIT = CF::N > 128 ? 227 : 624;
+};
+
+template <class CF>
+static void load_planes(const int8_t* b, typename CF::Bd* P, const typename CF::Dim& dm) {
+    if constexpr (CF::DYN) {
+        frame_from_bytes<CF>(reinterpret_cast<const uint8_t*>(b), P, dm);
+    } else {
+        uint32_t cw[(CF::N + 3) / 4];
+        memset(cw, 0, sizeof(cw));
+        memcpy(cw, b, CF::N);
+        planes_from_words<CF>(cw, P);
+    }
+}
+
+template <class CF>
+static void legal_of(const int8_t* b, typename CF::Bd* P, uint32_t* act, const typename CF::Dim& dm) {
+    typename CF::Bd HL, VL;
+    load_planes<CF>(b, P, dm);
+    legal_masks<CF>(P, special_mask<CF, CF::NP>(P), HL, VL, dm);
+    uint32_t a[CF::AW];
+    action_bits<CF>(HL, VL, a, dm);
+    for (int i = 0; i < CF::AW; ++i) act[i] = i < dm.aw() ? a[i] : 0u;
+}
+
+// stats: [0] candidates, [1] candidates the fast path gave up, [2] boards handed to the exact pass
+template <class CF>
+static int lookahead_n(int bpw, long n, const int8_t* boards, const uint32_t* seeds, const int32_t* nact,
+                       int32_t* best_action, int32_t* best_reward, int32_t* values, uint32_t* last_draws,
+                       uint32_t* flags, long* stats) {
+    const typename CF::Dim dm(g_shape);
+    const int NC = dm.cells(), A = dm.actions(), AW = dm.aw();
+    if (bpw < 1 || bpw > 64) return -1;
+    std::vector<uint32_t> act_s((size_t)bpw * CF::AW), pre_s(bpw + 1), m397_s(bpw);
+    std::vector<LookAcc> acc_s(bpw);
+    std::vector<long> redo;
+    auto* st = new SmallStore<CF, HK<CF>::GCAP>;
+    for (long b0 = 0; b0 < n; b0 += bpw) {
+        const int nb = (int)((n - b0) < bpw ? (n - b0) : bpw);
+        uint32_t run = 0;
+        for (int t = 0; t < nb; ++t) {  // the legal phase: lane t, board t
+            typename CF::Bd P[CF::NP];
+            legal_of<CF>(boards + (b0 + t) * NC, P, &act_s[(size_t)t * CF::AW], dm);
+            const uint32_t cnt = look_count(&act_s[(size_t)t * CF::AW], AW);
+            pre_s[t] = run;
+            run += cnt;
+            m397_s[t] = mt_state397(seeds[b0 + t]);
+            look_acc_init(acc_s[t], nact[b0 + t], cnt);
+        }
+        pre_s[nb] = run;
+        const uint32_t total = run;
+        if (values)
+            for (int i = 0; i < nb * A; ++i) {
+                const int g = i / A, id = i - g * A;
+                if (!((act_s[(size_t)g * CF::AW + (id >> 5)] >> (id & 31)) & 1u)) values[(b0 + g) * A + id] = -1;
+            }
+        for (uint32_t base = 0; base < total; base += 64u)
+            for (uint32_t lane = 0; lane < 64u; ++lane) {
+                const uint32_t j = base + lane;
+                if (j >= total) continue;
+                const int g = look_find_board(pre_s.data(), nb, j);
+                if (g < 0 || g >= nb || pre_s[g] > j || j >= pre_s[g + 1]) return -2;
+                const int action = look_kth_bit(&act_s[(size_t)g * CF::AW], AW, j - pre_s[g]);
+                if (action < 0 || action >= A) return -3;
+                typename CF::Bd P[CF::NP];
+                load_planes<CF>(boards + (b0 + g) * NC, P, dm);
+                const LookCand c = look_eval<CF, typename HK<CF>::Chain>(P, seeds[b0 + g], m397_s[g], nact[b0 + g],
+                                                                        action, *st, dm);
+                if (values && !c.redo) values[(b0 + g) * A + action] = c.reward;
+                look_fold(&acc_s[g], c, action, j + 1u == pre_s[g + 1]);
+                stats[0]++;
+                stats[1] += c.redo;
+            }
+        for (int t = 0; t < nb; ++t) {
+            const LookAcc& acc = acc_s[t];
+            if (acc.redo) {
+                redo.push_back(b0 + t);
+                continue;
+            }
+            if (best_action) best_action[b0 + t] = look_key_action(acc.key);
+            if (best_reward) best_reward[b0 + t] = look_key_reward(acc.key);
+            if (last_draws) last_draws[b0 + t] = acc.last_draws;
+            if (flags) flags[b0 + t] = acc.flags;
+        }
+    }
+    delete st;
+    auto* mt = new FullMT;
+    auto* as = new ArrayStore<CF>;
+    for (long b : redo) {  // the exact pass (k_lookahead_fix), one lane
+        typename CF::Bd P[CF::NP];
+        uint32_t act[CF::AW];
+        legal_of<CF>(boards + b * NC, P, act, dm);
+        uint64_t key = LOOK_KEY_NONE;
+        uint32_t fl = 0u, ld = 0u;
+        look_exact<CF>(P, act, seeds[b], nact[b], 0u, 1u, key, fl, ld, values ? values + b * A : nullptr, *mt, *as, dm);
+        LookAcc acc;
+        look_acc_init(acc, nact[b], look_count(act, AW));
+        if (best_action) best_action[b] = look_key_action(key);
+        if (best_reward) best_reward[b] = look_key_reward(key);
+        if (last_draws) last_draws[b] = ld;
+        if (flags) flags[b] = fl | acc.flags;
+        stats[2]++;
+    }
+    delete mt;
+    delete as;
+    return 0;
+}
+
+using C9 = Cfg<9, 9, 6>;
+using C16 = Cfg<16, 16, 8>;
+#define LH_DISPATCH(cfg, call)                     \
+    do {                                           \
+        if (cfg == 0) {                            \
+            call(C9);                              \
+        } else if (cfg == 1) {                     \
+            call(C16);                             \
+        } else if (g_shape.fs != 16) {             \
+            return -9;                             \
+        } else {                                   \
+            const int bits_ = bits_for_types(g_T); \
+            if (bits_ == 2) {                      \
+                call(FCfg<2>);                     \
+            } else if (bits_ == 3) {               \
+                call(FCfg<3>);                     \
+            } else if (bits_ == 4) {               \
+                call(FCfg<4>);                     \
+            } else {                               \
+                call(FCfg<5>);                     \
+            }                                      \
+        }                                          \
+    } while (0)
+
+extern "C" {
+
+int lh_set_frame(int rows, int columns, int types) {
+    if (rows < 3 || rows > 16 || columns < 3 || columns > 16 || types < 2 || types > 31) return -1;
+    g_T = types;
+    g_shape = make_shape(rows, columns, types);
+    return 0;
+}
+
+int lh_lookahead(int cfg, int bpw, long n, const int8_t* boards, const uint32_t* seeds, const int32_t* nact,
+                 int32_t* best_action, int32_t* best_reward, int32_t* values, uint32_t* last_draws, uint32_t* flags,
+                 long* stats) {
+    int rc = 0;
+    stats[0] = stats[1] = stats[2] = 0;
+#define CALL(CF) rc = lookahead_n<CF>(bpw, n, boards, seeds, nact, best_action, best_reward, values, last_draws, flags, stats)
+    LH_DISPATCH(cfg, CALL);
+#undef CALL
+    return rc;
+}
+
+int lh_gcap(int cfg) {
+    int rc = 0;
+#define CALL(CF) rc = HK<CF>::GCAP
+    LH_DISPATCH(cfg, CALL);
+#undef CALL
+    return rc;
+}
+
+int lh_chain_limit(int cfg) {
+    int rc = 0;
+#define CALL(CF) rc = HK<CF>::LIMIT
+    LH_DISPATCH(cfg, CALL);
+#undef CALL
+    return rc;
+}
+
+// the key and the enumeration on their own
+unsigned long long lh_key(int32_t reward, int action) { return look_key(reward, action); }
+int32_t lh_key_reward(unsigned long long key) { return look_key_reward(key); }
+int32_t lh_key_action(unsigned long long key) { return look_key_action(key); }
+int lh_find_board(const uint32_t* pre, int nb, uint32_t j) { return look_find_board(pre, nb, j); }
+int lh_kth_bit(const uint32_t* act, int aw, uint32_t k) { return look_kth_bit(act, aw, k); }
+// fold (reward[i], action[i]) in the given order; the result must not depend on it
+unsigned long long lh_fold(int n, const int32_t* reward, const int32_t* action) {
+    LookAcc acc;
+    look_acc_init(acc, 1, (uint32_t)n);
+    for (int i = 0; i < n; ++i) {
+        LookCand c{reward[i], 0u, 0u, false};
+        look_fold(&acc, c, action[i], false);
+    }
+    return acc.key;
+}
+
+}  // extern "C"
