@@ -60,44 +60,6 @@ int ensure_scratch(m3_ctx* c, size_t bytes) {
     return M3_OK;
 }
 
-struct Carve {
-    char* base;
-    size_t off = 0;
-    template <class T>
-    T* take(size_t count) {
-        off = (off + 255) & ~size_t(255);
-        T* p = reinterpret_cast<T*>(base + off);
-        off += count * sizeof(T);
-        return p;
-    }
-};
-
-size_t carve_size(std::initializer_list<size_t> sizes) {
-    size_t s = 0;
-    for (size_t v : sizes) s = ((s + 255) & ~size_t(255)) + v;
-    return s + 256;
-}
-
-// Host-buffer calls stage through one pinned image per direction: the caller's
-// inputs are packed into the context's pinned buffer and go up in ONE copy
-// (which also zeroes the launch's counters, part of the image), the outputs
-// come back in ONE copy and are unpacked -- for the BoardV2 facade's batch-1
-// calls that is two copies, the launches and a sync, instead of a pageable
-// copy per array.
-struct Image {
-    static constexpr int MAXP = 12;
-    size_t off[MAXP] = {}, size[MAXP] = {};
-    int n = 0;
-    size_t total = 0;
-    int add(size_t bytes) {
-        total = (total + 255) & ~size_t(255);
-        off[n] = total;
-        size[n] = bytes;
-        total += bytes;
-        return n++;
-    }
-};
-
 int ensure_host(m3_ctx* c, size_t bytes) {
     if (c->hcap >= bytes) return M3_OK;
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -111,63 +73,108 @@ int ensure_host(m3_ctx* c, size_t bytes) {
     return M3_OK;
 }
 
-// Device scratch = [input image | output image | device-only tail]; the pinned
-// buffer holds the larger of the two images. Returns the device base.
-int stage_begin(m3_ctx* c, const Image& in, const Image& out, size_t tail, char** dev) {
-    const size_t in_sz = (in.total + 255) & ~size_t(255), out_sz = (out.total + 255) & ~size_t(255);
-    int rc = ensure_scratch(c, in_sz + out_sz + tail + 256);
-    if (rc) return rc;
-    rc = ensure_host(c, std::max(in_sz, out_sz) + 256);
-    if (rc) return rc;
-    *dev = (char*)c->dbuf;
-    return M3_OK;
-}
+constexpr size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
-// pack host inputs and upload the image; the same copy zeroes the first
-// `zero_out` bytes of the output image that follows it (the launch's counters)
-int stage_upload(m3_ctx* c, const Image& in, std::initializer_list<const void*> srcs, char* dev,
-                 size_t zero_out = 0) {
-    char* h = (char*)c->hbuf;
-    int i = 0;
-    for (const void* p : srcs) {
-        memcpy(h + in.off[i], p, in.size[i]);
-        ++i;
-    }
-    const size_t in_sz = (in.total + 255) & ~size_t(255);
-    memset(h + in.total, 0, in_sz + zero_out - in.total);
-    HIP_TRY(hipMemcpyAsync(dev, h, in_sz + zero_out, hipMemcpyHostToDevice, c->stream));
-    return M3_OK;
-}
+// Small host-buffer calls (the facade's batch-1 calls) run zero-copy; m3_rollouts is staged at every n.
+constexpr int64_t ZC_MAX_BOARDS = 256;
+constexpr int ZC_OVF_WORD = 8;  // c->counters[8]: the zero-copy overflow count, kept zero between calls
 
-// download the output image, wait, unpack into the caller's buffers (nullptr = skip)
-int stage_download(m3_ctx* c, const Image& out, std::initializer_list<void*> dsts, const char* dev) {
-    char* h = (char*)c->hbuf;
-    HIP_TRY(hipMemcpyAsync(h, dev, out.total, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    int i = 0;
-    for (void* p : dsts) {
-        if (p) memcpy(p, h + out.off[i], out.size[i]);
-        ++i;
+// One host-buffer call. The call registers its parts once (input / output, each 256-byte aligned),
+// then begin() -> fill the kernel arguments from dev() / lead_dev() / tail() -> launch -> finish().
+//   staged:    the inputs are packed into the context's pinned buffer and go up in ONE copy, which
+//              also zeroes the `lead` bytes in front of the outputs (the launch's counters); the
+//              outputs come back in ONE copy and are unpacked: two copies, the launches and a sync,
+//              instead of a pageable copy per array. Device scratch = [input image | output image
+//              | device-only tail]; the pinned buffer holds the larger of the two images.
+//   zero-copy: the kernels read the inputs from and write the outputs to the pinned buffer itself
+//              (host memory the device maps, one combined image), so a call is its launches and
+//              one sync, with no copy in either direction. The tail is the device scratch.
+class HostCall {
+public:
+    explicit HostCall(m3_ctx* c) : c_(c) {}
+    int input(const void* src, size_t bytes) { return add({bytes, src, nullptr, 0}, in_total_); }
+    // dst == nullptr: the caller does not want it (no bytes; its device address is nullptr)
+    int output(void* dst, size_t bytes) { return add({dst ? bytes : 0, nullptr, dst, 0}, out_total_); }
+
+    // lead: bytes in front of the outputs that are zero before the launch; tail: device-only bytes
+    int begin(bool zc, size_t lead, size_t tail) {
+        if (n_ > MAXP) return set_err(M3_ERR_INVALID, "internal: a host-buffer call with more than %d parts", MAXP);
+        zc_ = zc;
+        for (int i = 0; i < n_; ++i)
+            if (!parts_[i].src) parts_[i].off += align256(lead);  // the outputs follow the lead bytes
+        out_total_ += align256(lead);
+        const size_t in_sz = align256(in_total_), out_sz = align256(out_total_);
+        int rc = ensure_host(c_, (zc ? in_sz + out_total_ : std::max(in_sz, out_sz)) + 256);
+        const size_t scratch = zc ? tail : in_sz + out_sz + tail;
+        if (rc == M3_OK && scratch) rc = ensure_scratch(c_, scratch + 256);
+        if (rc) return rc;
+        char* h = (char*)c_->hbuf;  // (hbuf / hdev / dbuf are read only after they have grown)
+        din_ = (char*)(zc ? c_->hdev : c_->dbuf);
+        dout_ = din_ + in_sz;
+        hout_ = zc ? h + in_sz : h;
+        tail_ = zc ? (char*)c_->dbuf : dout_ + out_sz;
+        for (int i = 0; i < n_; ++i)
+            if (parts_[i].src) memcpy(h + parts_[i].off, parts_[i].src, parts_[i].bytes);
+        if (zc) {
+            memset(hout_, 0, lead);
+            return M3_OK;
+        }
+        memset(h + in_total_, 0, in_sz + lead - in_total_);
+        HIP_TRY(hipMemcpyAsync(din_, h, in_sz + lead, hipMemcpyHostToDevice, c_->stream));
+        return M3_OK;
     }
-    return M3_OK;
-}
+
+    template <class T>
+    T* dev(int part) const {
+        const Part& p = parts_[part];
+        return p.bytes ? reinterpret_cast<T*>((p.src ? din_ : dout_) + p.off) : nullptr;
+    }
+    uint32_t* lead_dev() const { return reinterpret_cast<uint32_t*>(dout_); }
+    const uint32_t* lead_host() const { return reinterpret_cast<const uint32_t*>(hout_); }  // after finish()
+    char* tail() const { return tail_; }
+
+    // wait for the launches (staged: behind the one download) and unpack the outputs
+    int finish() {
+        if (!zc_) HIP_TRY(hipMemcpyAsync(hout_, dout_, out_total_, hipMemcpyDeviceToHost, c_->stream));
+        HIP_TRY(hipStreamSynchronize(c_->stream));
+        for (int i = 0; i < n_; ++i)
+            if (parts_[i].dst) memcpy(parts_[i].dst, hout_ + parts_[i].off, parts_[i].bytes);
+        return M3_OK;
+    }
+
+private:
+    struct Part {
+        size_t bytes;
+        const void* src;  // input: the caller's buffer
+        void* dst;        // output: the caller's buffer
+        size_t off;       // in its image
+    };
+    // (a fixed array: no heap allocation per call. A part too many is only counted: begin() refuses the call.)
+    int add(Part p, size_t& total) {
+        if (n_ < MAXP) {
+            p.off = total = align256(total);
+            total += p.bytes;
+            parts_[n_] = p;
+        }
+        return n_++;
+    }
+    static constexpr int MAXP = 12;
+    m3_ctx* c_;
+    Part parts_[MAXP];
+    int n_ = 0;
+    size_t in_total_ = 0, out_total_ = 0;
+    bool zc_ = false;
+    char *din_ = nullptr, *dout_ = nullptr, *hout_ = nullptr, *tail_ = nullptr;
+};
 
 int bad_cells_error() {
     return set_err(M3_ERR_INVALID, "cell value outside [0, 127] in the boards (outputs undefined)");
 }
 
-// Zero-copy path of the small host-buffer calls (the facade's batch-1 calls): the kernels read
-// the inputs from and write the outputs to the context's pinned buffer (host memory the device
-// maps), so a call is its launches and one sync, with no copy in either direction.
-constexpr int64_t ZC_MAX_BOARDS = 256;
-constexpr int ZC_OVF_WORD = 8;  // c->counters[8]: the zero-copy overflow count, kept zero between calls
-
-
-
-
-
-
-
+int not_ready_error(const char* entry) {
+    return set_err(M3_ERR_STATE, "%s before m3_env_reset (or before m3_env_set of boards, seeds, score, moves and "
+                                 "next_action)", entry);
+}
 
 // Make `st` wait for every shard's last enqueued work.
 int join_shards(m3_env* e, hipStream_t st) {
@@ -198,6 +205,16 @@ void destroy_shards(m3_env* e) {
         for (hipEvent_t ev : sh.aev) (void)hipEventDestroy(ev);
     }
     e->shards.clear();
+}
+
+// A device buffer of the env: allocated into *field, recorded in e->owned (m3_env_destroy frees it),
+// and with `zero` filled with zeros on the context stream (the caller synchronises it).
+template <class T>
+hipError_t env_alloc(m3_env* e, T** field, size_t bytes, bool zero) {
+    hipError_t err = hipMalloc((void**)field, bytes ? bytes : 4);
+    if (err != hipSuccess) return err;
+    e->owned.push_back(*field);
+    return zero ? hipMemsetAsync(*field, 0, bytes, e->ctx->stream) : hipSuccess;
 }
 }  // namespace
 
@@ -350,53 +367,23 @@ int m3_init_boards_ex(m3_ctx* c, int64_t n, const uint32_t* seeds, int8_t* out_b
     CHECK_ARG(c && n >= 0 && (n == 0 || (seeds && out_boards)), "bad arguments");
     if (n == 0) return M3_OK;
     HIP_TRY(hipSetDevice(c->device));
-    if (n <= ZC_MAX_BOARDS) {  // zero-copy: the reset launch(es) and one sync
-        Image im;
-        const int i_s = im.add(n * 4ull), o_b = im.add(n * (size_t)c->N), o_d = im.add(n * 4ull),
-                  o_f = im.add(n * 4ull), o_g = im.add(n * 4ull);
-        int rc = ensure_host(c, im.total + 256);
-        if (rc) return rc;
-        char* h = (char*)c->hbuf;
-        char* d = (char*)c->hdev;
-        memcpy(h + im.off[i_s], seeds, n * 4);
-        InitArgs a{};
-        a.shape = c->sdesc;
-        a.n = n;
-        a.seeds = (const uint32_t*)(d + im.off[i_s]);
-        a.boards = (int8_t*)(d + im.off[o_b]);
-        a.draws = (uint32_t*)(d + im.off[o_d]);
-        a.first_action = (int32_t*)(d + im.off[o_f]);
-        a.flags = (uint32_t*)(d + im.off[o_g]);
-        rc = with_shape(c->shape, [&](auto cf) { return launch_init<decltype(cf)>(c->stream, a, n); });
-        if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        memcpy(out_boards, h + im.off[o_b], n * (size_t)c->N);
-        if (out_draws) memcpy(out_draws, h + im.off[o_d], n * 4);
-        if (out_first_action) memcpy(out_first_action, h + im.off[o_f], n * 4);
-        if (out_flags) memcpy(out_flags, h + im.off[o_g], n * 4);
-        return M3_OK;
-    }
-    Image in, out;
-    in.add(n * 4ull);
-    const int o_b = out.add(n * (size_t)c->N), o_d = out.add(n * 4ull), o_f = out.add(n * 4ull),
-              o_g = out.add(n * 4ull);
-    char* dev;
-    int rc = stage_begin(c, in, out, 0, &dev);
-    if (rc) return rc;
-    char* dout = dev + ((in.total + 255) & ~size_t(255));
-    rc = stage_upload(c, in, {seeds}, dev);
+    HostCall hc(c);
+    const int i_s = hc.input(seeds, n * 4ull);
+    const int o_b = hc.output(out_boards, n * (size_t)c->N), o_d = hc.output(out_draws, n * 4ull),
+              o_f = hc.output(out_first_action, n * 4ull), o_g = hc.output(out_flags, n * 4ull);
+    int rc = hc.begin(n <= ZC_MAX_BOARDS, 0, 0);
     if (rc) return rc;
     InitArgs a{};
     a.shape = c->sdesc;
     a.n = n;
-    a.seeds = (const uint32_t*)dev;
-    a.boards = (int8_t*)(dout + out.off[o_b]);
-    a.draws = (uint32_t*)(dout + out.off[o_d]);
-    a.first_action = (int32_t*)(dout + out.off[o_f]);
-    a.flags = (uint32_t*)(dout + out.off[o_g]);
+    a.seeds = hc.dev<const uint32_t>(i_s);
+    a.boards = hc.dev<int8_t>(o_b);
+    a.draws = hc.dev<uint32_t>(o_d);
+    a.first_action = hc.dev<int32_t>(o_f);
+    a.flags = hc.dev<uint32_t>(o_g);
     rc = with_shape(c->shape, [&](auto cf) { return launch_init<decltype(cf)>(c->stream, a, n); });
     if (rc) return rc;
-    return stage_download(c, out, {out_boards, out_draws, out_first_action, out_flags}, dout);
+    return hc.finish();
 }
 
 int m3_init_boards(m3_ctx* c, int64_t n, const uint32_t* seeds, int8_t* out_boards, uint32_t* out_draws,
@@ -419,139 +406,85 @@ int m3_apply_actions(m3_ctx* c, int64_t n, const int8_t* boards, const uint32_t*
     if (n == 0) return M3_OK;
     CHECK_ARG(boards && seeds && n_actions && actions && out_boards && out_reward && out_draws && out_flags,
               "null buffer");
-    int rc0 = check_ids_on_board(c);
-    if (rc0) return rc0;
+    int rc = check_ids_on_board(c);
+    if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const size_t bytes = n * (size_t)c->N;
-    if (n <= ZC_MAX_BOARDS) {  // zero-copy: two launches and one sync
-        Image im;
-        const int i_b = im.add(bytes), i_s = im.add(n * 4ull), i_na = im.add(n * 4ull), i_a = im.add(n * 4ull);
-        const int o_bad = im.add(16), o_b = im.add(bytes), o_r = im.add(n * 4ull), o_d = im.add(n * 4ull),
-                  o_f = im.add(n * 4ull), o_l = im.add(out_legal_bits ? n * 4ull * c->AW : 0),
-                  o_x = im.add(out_next_action ? n * 4ull : 0);
-        int rc = ensure_host(c, im.total + 256);
-        if (rc) return rc;
-        rc = ensure_scratch(c, n * 4ull + 256);
-        if (rc) return rc;
-        char* h = (char*)c->hbuf;  // host view
-        char* d = (char*)c->hdev;  // device view of the same pinned bytes
-        memcpy(h + im.off[i_b], boards, bytes);
-        memcpy(h + im.off[i_s], seeds, n * 4);
-        memcpy(h + im.off[i_na], n_actions, n * 4);
-        memcpy(h + im.off[i_a], actions, n * 4);
-        memset(h + im.off[o_bad], 0, 16);
-        ApplyArgs a{};
-        a.shape = c->sdesc;
-        a.n = n;
-        a.boards = (const int8_t*)(d + im.off[i_b]);
-        a.seeds = (const uint32_t*)(d + im.off[i_s]);
-        a.n_actions = (const int32_t*)(d + im.off[i_na]);
-        a.actions = (const int32_t*)(d + im.off[i_a]);
-        a.out_boards = (int8_t*)(d + im.off[o_b]);
-        a.reward = (int32_t*)(d + im.off[o_r]);
-        a.draws = (uint32_t*)(d + im.off[o_d]);
-        a.flags = (uint32_t*)(d + im.off[o_f]);
-        a.legal = out_legal_bits ? (uint32_t*)(d + im.off[o_l]) : nullptr;
-        a.next_action = out_next_action ? (int32_t*)(d + im.off[o_x]) : nullptr;
-        a.ovf_count = c->counters + ZC_OVF_WORD;
-        a.bad_cells = (uint32_t*)(d + im.off[o_bad]);
-        a.ovf_list = (uint32_t*)c->dbuf;
-        a.clear_ovf = 1;
-        rc = with_shape(c->shape, [&](auto cf) { return launch_apply<decltype(cf)>(c, a); });
-        if (rc) {  // k_apply may have counted overflows that k_apply_fix never cleared: the next
-                   // call must not read them (best effort; the launch error is what is reported)
-            (void)hipMemsetAsync(a.ovf_count, 0, 4, c->stream);  // (ordered before the next call's kernels)
-            (void)hipStreamSynchronize(c->stream);
-            return rc;
-        }
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (*(volatile uint32_t*)(h + im.off[o_bad])) return bad_cells_error();
-        memcpy(out_boards, h + im.off[o_b], bytes);
-        memcpy(out_reward, h + im.off[o_r], n * 4);
-        memcpy(out_draws, h + im.off[o_d], n * 4);
-        memcpy(out_flags, h + im.off[o_f], n * 4);
-        if (out_legal_bits) memcpy(out_legal_bits, h + im.off[o_l], n * 4ull * c->AW);
-        if (out_next_action) memcpy(out_next_action, h + im.off[o_x], n * 4);
-        return M3_OK;
-    }
-    Image in, out;  // cell values are checked on the device while the boards are staged (k_apply)
-    const int i_b = in.add(bytes), i_s = in.add(n * 4ull), i_na = in.add(n * 4ull), i_a = in.add(n * 4ull);
-    const int o_cnt = out.add(16), o_b = out.add(bytes), o_r = out.add(n * 4ull), o_d = out.add(n * 4ull),
-              o_f = out.add(n * 4ull), o_l = out.add(out_legal_bits ? n * 4ull * c->AW : 0),
-              o_x = out.add(out_next_action ? n * 4ull : 0);
-    char* dev;
-    int rc = stage_begin(c, in, out, n * 4ull, &dev);
-    if (rc) return rc;
-    char* dout = dev + ((in.total + 255) & ~size_t(255));
-    char* dtail = dout + ((out.total + 255) & ~size_t(255));
-    rc = stage_upload(c, in, {boards, seeds, n_actions, actions}, dev, 16);
+    const bool zc = n <= ZC_MAX_BOARDS;
+    HostCall hc(c);  // cell values are checked on the device while the boards are staged (k_apply)
+    const int i_b = hc.input(boards, bytes), i_s = hc.input(seeds, n * 4ull), i_na = hc.input(n_actions, n * 4ull),
+              i_a = hc.input(actions, n * 4ull);
+    const int o_b = hc.output(out_boards, bytes), o_r = hc.output(out_reward, n * 4ull),
+              o_d = hc.output(out_draws, n * 4ull), o_f = hc.output(out_flags, n * 4ull),
+              o_l = hc.output(out_legal_bits, n * 4ull * c->AW), o_x = hc.output(out_next_action, n * 4ull);
+    rc = hc.begin(zc, 16, n * 4ull);  // lead words: [0] overflow count (staged), [1] bad cells; tail: overflow list
     if (rc) return rc;
     ApplyArgs a{};
     a.shape = c->sdesc;
     a.n = n;
-    a.boards = (const int8_t*)(dev + in.off[i_b]);
-    a.seeds = (const uint32_t*)(dev + in.off[i_s]);
-    a.n_actions = (const int32_t*)(dev + in.off[i_na]);
-    a.actions = (const int32_t*)(dev + in.off[i_a]);
-    a.out_boards = (int8_t*)(dout + out.off[o_b]);
-    a.reward = (int32_t*)(dout + out.off[o_r]);
-    a.draws = (uint32_t*)(dout + out.off[o_d]);
-    a.flags = (uint32_t*)(dout + out.off[o_f]);
-    a.legal = out_legal_bits ? (uint32_t*)(dout + out.off[o_l]) : nullptr;
-    a.next_action = out_next_action ? (int32_t*)(dout + out.off[o_x]) : nullptr;
-    a.ovf_count = (uint32_t*)(dout + out.off[o_cnt]);  // zeroed by the upload, returned with the outputs
-    a.bad_cells = a.ovf_count + 1;
-    a.ovf_list = (uint32_t*)dtail;
+    a.boards = hc.dev<const int8_t>(i_b);
+    a.seeds = hc.dev<const uint32_t>(i_s);
+    a.n_actions = hc.dev<const int32_t>(i_na);
+    a.actions = hc.dev<const int32_t>(i_a);
+    a.out_boards = hc.dev<int8_t>(o_b);
+    a.reward = hc.dev<int32_t>(o_r);
+    a.draws = hc.dev<uint32_t>(o_d);
+    a.flags = hc.dev<uint32_t>(o_f);
+    a.legal = hc.dev<uint32_t>(o_l);
+    a.next_action = hc.dev<int32_t>(o_x);
+    // zero-copy: the count is a device word that k_apply_fix, launched with one block, clears again;
+    // staged: lead word 0, zeroed by the upload
+    a.ovf_count = zc ? c->counters + ZC_OVF_WORD : hc.lead_dev();
+    a.clear_ovf = zc ? 1 : 0;
+    a.bad_cells = hc.lead_dev() + 1;
+    a.ovf_list = (uint32_t*)hc.tail();
     rc = with_shape(c->shape, [&](auto cf) { return launch_apply<decltype(cf)>(c, a); });
+    if (rc) {
+        if (zc) {  // k_apply may have counted overflows that k_apply_fix never cleared: the next
+                   // call must not read them (best effort; the launch error is what is reported)
+            (void)hipMemsetAsync(a.ovf_count, 0, 4, c->stream);  // (ordered before the next call's kernels)
+            (void)hipStreamSynchronize(c->stream);
+        }
+        return rc;
+    }
+    rc = hc.finish();
     if (rc) return rc;
-    uint32_t cnt[4];
-    rc = stage_download(c, out, {cnt, out_boards, out_reward, out_draws, out_flags, out_legal_bits,
-                                 out_next_action}, dout);
-    if (rc) return rc;
-    return cnt[1] ? bad_cells_error() : M3_OK;
+    return hc.lead_host()[1] ? bad_cells_error() : M3_OK;
 }
 
 int m3_legal_actions(m3_ctx* c, int64_t n, const int8_t* boards, uint32_t* out_legal_bits) {
     CHECK_ARG(c && n >= 0, "bad arguments");
     if (n == 0) return M3_OK;
     CHECK_ARG(boards && out_legal_bits, "null buffer");
-    int rc0 = check_ids_on_board(c);
-    if (rc0) return rc0;
-    HIP_TRY(hipSetDevice(c->device));
-    if (n <= ZC_MAX_BOARDS) {  // zero-copy: one launch and one sync
-        Image im;
-        const int i_b = im.add(n * (size_t)c->N), o_l = im.add(n * 4ull * c->AW);
-        int rc = ensure_host(c, im.total + 256);
-        if (rc) return rc;
-        char* h = (char*)c->hbuf;
-        char* d = (char*)c->hdev;
-        memcpy(h + im.off[i_b], boards, n * (size_t)c->N);
-        rc = with_shape(c->shape, [&](auto cf) {
-            return launch_legal<decltype(cf)>(c, n, (const int8_t*)(d + im.off[i_b]), (uint32_t*)(d + im.off[o_l]));
-        });
-        if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        memcpy(out_legal_bits, h + im.off[o_l], n * 4ull * c->AW);
-        return M3_OK;
-    }
-    Image in, out;
-    in.add(n * (size_t)c->N);
-    out.add(n * 4ull * c->AW);
-    char* dev;
-    int rc = stage_begin(c, in, out, 0, &dev);
+    int rc = check_ids_on_board(c);
     if (rc) return rc;
-    char* dout = dev + ((in.total + 255) & ~size_t(255));
-    rc = stage_upload(c, in, {boards}, dev);
+    HIP_TRY(hipSetDevice(c->device));
+    HostCall hc(c);
+    const int i_b = hc.input(boards, n * (size_t)c->N), o_l = hc.output(out_legal_bits, n * 4ull * c->AW);
+    rc = hc.begin(n <= ZC_MAX_BOARDS, 0, 0);
     if (rc) return rc;
     rc = with_shape(c->shape, [&](auto cf) {
-        return launch_legal<decltype(cf)>(c, n, (const int8_t*)dev, (uint32_t*)dout);
+        return launch_legal<decltype(cf)>(c, n, hc.dev<const int8_t>(i_b), hc.dev<uint32_t>(o_l));
     });
     if (rc) return rc;
-    return stage_download(c, out, {out_legal_bits}, dout);
+    return hc.finish();
 }
 
 // ---- one-ply lookahead --------------------------------------------------------
 constexpr int LOOK_OVF_WORD = 12;  // c->counters[12]: the lookahead's exact-pass count (zeroed per call)
+
+// The checks that the host-buffer and the device-buffer form of a batch call share; the caller
+// returns at once if this fails or n == 0. `buffers`: every required pointer is non-null.
+static int batch_call_preamble(m3_ctx* c, int64_t n, bool buffers) {
+    CHECK_ARG(c && n >= 0, "bad arguments");
+    if (n == 0) return M3_OK;
+    CHECK_ARG(n < (int64_t)1 << 31, "n too large");
+    CHECK_ARG(buffers, "null buffer");
+    int rc = check_ids_on_board(c);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return M3_OK;
+}
 
 // a.n, the inputs and the outputs set; the exact pass's list comes from `list` ([n] words of device memory)
 static int enqueue_lookahead(m3_ctx* c, LookArgs a, uint32_t* list) {
@@ -565,13 +498,8 @@ static int enqueue_lookahead(m3_ctx* c, LookArgs a, uint32_t* list) {
 int m3_lookahead_device(m3_ctx* c, int64_t n, const int8_t* boards, const uint32_t* seeds, const int32_t* n_actions,
                         int32_t* out_best_action, int32_t* out_best_reward, int32_t* out_values,
                         uint32_t* out_last_draws, uint32_t* out_flags) {
-    CHECK_ARG(c && n >= 0, "bad arguments");
-    if (n == 0) return M3_OK;
-    CHECK_ARG(n < (int64_t)1 << 31, "n too large");
-    CHECK_ARG(boards && seeds && n_actions, "null buffer");
-    int rc = check_ids_on_board(c);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
+    int rc = batch_call_preamble(c, n, boards && seeds && n_actions);
+    if (rc || n == 0) return rc;
     rc = ensure_scratch(c, n * 4ull + 256);
     if (rc) return rc;
     LookArgs a{};
@@ -590,67 +518,32 @@ int m3_lookahead_device(m3_ctx* c, int64_t n, const int8_t* boards, const uint32
 int m3_lookahead(m3_ctx* c, int64_t n, const int8_t* boards, const uint32_t* seeds, const int32_t* n_actions,
                  int32_t* out_best_action, int32_t* out_best_reward, int32_t* out_values, uint32_t* out_last_draws,
                  uint32_t* out_flags) {
-    CHECK_ARG(c && n >= 0, "bad arguments");
-    if (n == 0) return M3_OK;
-    CHECK_ARG(n < (int64_t)1 << 31, "n too large");
-    CHECK_ARG(boards && seeds && n_actions, "null buffer");
-    int rc = check_ids_on_board(c);
+    int rc = batch_call_preamble(c, n, boards && seeds && n_actions);
+    if (rc || n == 0) return rc;
+    HostCall hc(c);
+    const int i_b = hc.input(boards, n * (size_t)c->N), i_s = hc.input(seeds, n * 4ull),
+              i_na = hc.input(n_actions, n * 4ull);
+    const int o_a = hc.output(out_best_action, n * 4ull), o_r = hc.output(out_best_reward, n * 4ull),
+              o_v = hc.output(out_values, n * 4ull * c->A), o_d = hc.output(out_last_draws, n * 4ull),
+              o_f = hc.output(out_flags, n * 4ull);
+    rc = hc.begin(n <= ZC_MAX_BOARDS, 16, n * 4ull);  // lead word [0]: bad cells; tail: the exact pass's list
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t bytes = n * (size_t)c->N, vbytes = out_values ? n * 4ull * c->A : 0;
-    const bool zc = n <= ZC_MAX_BOARDS;  // zero-copy: the kernels read and write the pinned buffer
-    Image in, out;
-    Image& im_out = zc ? in : out;  // (zero-copy: one image holds both)
-    const int i_b = in.add(bytes), i_s = in.add(n * 4ull), i_na = in.add(n * 4ull);
-    const int o_bad = im_out.add(16), o_a = im_out.add(out_best_action ? n * 4ull : 0),
-              o_r = im_out.add(out_best_reward ? n * 4ull : 0), o_v = im_out.add(vbytes),
-              o_d = im_out.add(out_last_draws ? n * 4ull : 0), o_f = im_out.add(out_flags ? n * 4ull : 0);
-    char *din, *dout, *hout;
-    uint32_t* list;
-    if (zc) {
-        rc = ensure_host(c, in.total + 256);
-        if (rc) return rc;
-        rc = ensure_scratch(c, n * 4ull + 256);
-        if (rc) return rc;
-        char* h = (char*)c->hbuf;
-        memcpy(h + in.off[i_b], boards, bytes);
-        memcpy(h + in.off[i_s], seeds, n * 4);
-        memcpy(h + in.off[i_na], n_actions, n * 4);
-        memset(h + in.off[o_bad], 0, 16);
-        din = dout = (char*)c->hdev;
-        hout = h;
-        list = (uint32_t*)c->dbuf;
-    } else {
-        rc = stage_begin(c, in, out, n * 4ull, &din);
-        if (rc) return rc;
-        dout = din + ((in.total + 255) & ~size_t(255));
-        list = (uint32_t*)(dout + ((out.total + 255) & ~size_t(255)));
-        rc = stage_upload(c, in, {boards, seeds, n_actions}, din, 16);  // (zeroes the bad-cell word)
-        if (rc) return rc;
-        hout = (char*)c->hbuf;
-    }
     LookArgs a{};
     a.n = n;
-    a.boards = (const int8_t*)(din + in.off[i_b]);
-    a.seeds = (const uint32_t*)(din + in.off[i_s]);
-    a.n_actions = (const int32_t*)(din + in.off[i_na]);
-    a.bad_cells = (uint32_t*)(dout + im_out.off[o_bad]);
-    a.best_action = out_best_action ? (int32_t*)(dout + im_out.off[o_a]) : nullptr;
-    a.best_reward = out_best_reward ? (int32_t*)(dout + im_out.off[o_r]) : nullptr;
-    a.values = out_values ? (int32_t*)(dout + im_out.off[o_v]) : nullptr;
-    a.last_draws = out_last_draws ? (uint32_t*)(dout + im_out.off[o_d]) : nullptr;
-    a.flags = out_flags ? (uint32_t*)(dout + im_out.off[o_f]) : nullptr;
-    rc = enqueue_lookahead(c, a, list);
+    a.boards = hc.dev<const int8_t>(i_b);
+    a.seeds = hc.dev<const uint32_t>(i_s);
+    a.n_actions = hc.dev<const int32_t>(i_na);
+    a.bad_cells = hc.lead_dev();
+    a.best_action = hc.dev<int32_t>(o_a);
+    a.best_reward = hc.dev<int32_t>(o_r);
+    a.values = hc.dev<int32_t>(o_v);
+    a.last_draws = hc.dev<uint32_t>(o_d);
+    a.flags = hc.dev<uint32_t>(o_f);
+    rc = enqueue_lookahead(c, a, (uint32_t*)hc.tail());
     if (rc) return rc;
-    if (!zc) HIP_TRY(hipMemcpyAsync(hout, dout, out.total, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (*(volatile uint32_t*)(hout + im_out.off[o_bad])) return bad_cells_error();
-    if (out_best_action) memcpy(out_best_action, hout + im_out.off[o_a], n * 4);
-    if (out_best_reward) memcpy(out_best_reward, hout + im_out.off[o_r], n * 4);
-    if (out_values) memcpy(out_values, hout + im_out.off[o_v], vbytes);
-    if (out_last_draws) memcpy(out_last_draws, hout + im_out.off[o_d], n * 4);
-    if (out_flags) memcpy(out_flags, hout + im_out.off[o_f], n * 4);
-    return M3_OK;
+    rc = hc.finish();
+    if (rc) return rc;
+    return hc.lead_host()[0] ? bad_cells_error() : M3_OK;
 }
 
 // ---- rollouts ---------------------------------------------------------------
@@ -658,10 +551,9 @@ int m3_lookahead(m3_ctx* c, int64_t n, const int8_t* boards, const uint32_t* see
 
 namespace {
 
-// overflow list + group-table spill pool of a rollout launch (a lane keeps one
-// spill record for its whole rollout)
-// records of the rollout spill pool: one per 8 rollouts (at least 4096), within 256 MB (a lane
-// that finds the pool empty is replayed exactly by k_rollout_fix)
+// records of the rollout spill pool (a lane keeps one spill record for its whole rollout): one per
+// 8 rollouts (at least 4096), within 256 MB (a lane that finds the pool empty is replayed exactly
+// by k_rollout_fix)
 int64_t rollout_spill_cap(int64_t n, size_t words) {
     const int64_t budget = (int64_t)((256ull << 20) / (words * 4ull));
     return std::max<int64_t>(1, std::min(std::max<int64_t>(4096, n / 8), budget));
@@ -674,18 +566,24 @@ size_t rollout_spill_words(int shape) {
     });
 }
 
-// a.n and the per-rollout buffers set; carves the pool from cv and launches.
+// device-only bytes of a rollout launch: [overflow list, n words | spill pool], each 256-byte aligned
+size_t rollout_pool_bytes(int shape, int64_t n) {
+    return rollout_spill_cap(n, rollout_spill_words(shape)) * rollout_spill_words(shape) * 4ull;
+}
+size_t rollout_tail_bytes(int shape, int64_t n) { return align256(n * 4ull) + rollout_pool_bytes(shape, n) + 256; }
+
+// a.n and the per-rollout buffers set; `tail`: rollout_tail_bytes of device memory, 256-byte aligned.
 // counters: 16 zeroed bytes on the device (nullptr: the context's, zeroed here)
-int enqueue_rollouts(m3_ctx* c, RolloutArgs a, Carve& cv, uint32_t* counters = nullptr) {
-    const int64_t cap = rollout_spill_cap(a.n, rollout_spill_words(c->shape));
+int enqueue_rollouts(m3_ctx* c, RolloutArgs a, char* tail, uint32_t* counters = nullptr) {
     if (!counters) {
         counters = c->counters;
         HIP_TRY(hipMemsetAsync(counters, 0, 16, c->stream));
     }
+    a.shape = c->sdesc;
     a.counters = counters;
-    a.ovf_list = cv.take<uint32_t>(a.n);
-    a.spill = cv.take<uint32_t>(cap * rollout_spill_words(c->shape));
-    a.spill_cap = (uint32_t)cap;
+    a.ovf_list = (uint32_t*)tail;
+    a.spill = (uint32_t*)(tail + align256(a.n * 4ull));
+    a.spill_cap = (uint32_t)rollout_spill_cap(a.n, rollout_spill_words(c->shape));
     return with_shape(c->shape, [&](auto cf) { return launch_rollouts<decltype(cf)>(c, a); });
 }
 
@@ -696,19 +594,12 @@ extern "C" {
 int m3_rollouts_device(m3_ctx* c, int64_t n, const int8_t* boards, const uint32_t* seeds, const int32_t* n_actions,
                        const uint32_t* rollout_seeds, int32_t* out_gain, int32_t* out_steps, uint32_t* out_draws,
                        uint32_t* out_flags, int8_t* out_boards) {
-    CHECK_ARG(c && n >= 0, "bad arguments");
-    if (n == 0) return M3_OK;
-    CHECK_ARG(n < (int64_t)1 << 31, "n too large");
-    CHECK_ARG(boards && seeds && n_actions && rollout_seeds && out_gain && out_steps && out_draws && out_flags,
-              "null buffer");
-    int rc0 = check_ids_on_board(c);
-    if (rc0) return rc0;
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = ensure_scratch(c, carve_size({n * 4ull, rollout_spill_cap(n, rollout_spill_words(c->shape)) * rollout_spill_words(c->shape) * 4ull}));
+    int rc = batch_call_preamble(c, n, boards && seeds && n_actions && rollout_seeds && out_gain && out_steps &&
+                                           out_draws && out_flags);
+    if (rc || n == 0) return rc;
+    rc = ensure_scratch(c, rollout_tail_bytes(c->shape, n));
     if (rc) return rc;
-    Carve cv{(char*)c->dbuf};
     RolloutArgs a{};
-    a.shape = c->sdesc;
     a.n = n;
     a.boards = boards;
     a.seeds = seeds;
@@ -719,52 +610,40 @@ int m3_rollouts_device(m3_ctx* c, int64_t n, const int8_t* boards, const uint32_
     a.draws = out_draws;
     a.flags = out_flags;
     a.out_boards = out_boards;
-    return enqueue_rollouts(c, a, cv);
+    return enqueue_rollouts(c, a, (char*)c->dbuf);
 }
 
 int m3_rollouts(m3_ctx* c, int64_t n, const int8_t* boards, const uint32_t* seeds, const int32_t* n_actions,
                 const uint32_t* rollout_seeds, int32_t* out_gain, int32_t* out_steps, uint32_t* out_draws,
                 uint32_t* out_flags, int8_t* out_boards) {
-    CHECK_ARG(c && n >= 0, "bad arguments");
-    if (n == 0) return M3_OK;
-    CHECK_ARG(n < (int64_t)1 << 31, "n too large");
-    CHECK_ARG(boards && seeds && n_actions && rollout_seeds && out_gain && out_steps && out_draws && out_flags,
-              "null buffer");
-    int rc0 = check_ids_on_board(c);
-    if (rc0) return rc0;
-    HIP_TRY(hipSetDevice(c->device));
+    int rc = batch_call_preamble(c, n, boards && seeds && n_actions && rollout_seeds && out_gain && out_steps &&
+                                           out_draws && out_flags);
+    if (rc || n == 0) return rc;
     const size_t bytes = n * (size_t)c->N;
-    Image in, out;  // cell values are checked on the device while the boards are staged (k_rollout)
-    const int i_b = in.add(bytes), i_s = in.add(n * 4ull), i_na = in.add(n * 4ull), i_rs = in.add(n * 4ull);
-    const int o_cnt = out.add(16), o_g = out.add(n * 4ull), o_st = out.add(n * 4ull), o_d = out.add(n * 4ull),
-              o_f = out.add(n * 4ull), o_b = out.add(out_boards ? bytes : 0);
-    const size_t tail = carve_size({n * 4ull, rollout_spill_cap(n, rollout_spill_words(c->shape)) * rollout_spill_words(c->shape) * 4ull});
-    char* dev;
-    int rc = stage_begin(c, in, out, tail, &dev);
-    if (rc) return rc;
-    char* dout = dev + ((in.total + 255) & ~size_t(255));
-    char* dtail = dout + ((out.total + 255) & ~size_t(255));
-    rc = stage_upload(c, in, {boards, seeds, n_actions, rollout_seeds}, dev, 16);
+    HostCall hc(c);  // cell values are checked on the device while the boards are staged (k_rollout)
+    const int i_b = hc.input(boards, bytes), i_s = hc.input(seeds, n * 4ull), i_na = hc.input(n_actions, n * 4ull),
+              i_rs = hc.input(rollout_seeds, n * 4ull);
+    const int o_g = hc.output(out_gain, n * 4ull), o_st = hc.output(out_steps, n * 4ull),
+              o_d = hc.output(out_draws, n * 4ull), o_f = hc.output(out_flags, n * 4ull),
+              o_b = hc.output(out_boards, bytes);
+    rc = hc.begin(false, 16, rollout_tail_bytes(c->shape, n));  // staged at every n; lead: the launch's counters
     if (rc) return rc;
     RolloutArgs a{};
-    a.shape = c->sdesc;
     a.n = n;
-    a.boards = (const int8_t*)(dev + in.off[i_b]);
-    a.seeds = (const uint32_t*)(dev + in.off[i_s]);
-    a.n_actions = (const int32_t*)(dev + in.off[i_na]);
-    a.rseeds = (const uint32_t*)(dev + in.off[i_rs]);
-    a.gain = (int32_t*)(dout + out.off[o_g]);
-    a.steps = (int32_t*)(dout + out.off[o_st]);
-    a.draws = (uint32_t*)(dout + out.off[o_d]);
-    a.flags = (uint32_t*)(dout + out.off[o_f]);
-    a.out_boards = out_boards ? (int8_t*)(dout + out.off[o_b]) : nullptr;
-    Carve cv{dtail};
-    rc = enqueue_rollouts(c, a, cv, (uint32_t*)(dout + out.off[o_cnt]));  // zeroed by the upload
+    a.boards = hc.dev<const int8_t>(i_b);
+    a.seeds = hc.dev<const uint32_t>(i_s);
+    a.n_actions = hc.dev<const int32_t>(i_na);
+    a.rseeds = hc.dev<const uint32_t>(i_rs);
+    a.gain = hc.dev<int32_t>(o_g);
+    a.steps = hc.dev<int32_t>(o_st);
+    a.draws = hc.dev<uint32_t>(o_d);
+    a.flags = hc.dev<uint32_t>(o_f);
+    a.out_boards = hc.dev<int8_t>(o_b);
+    rc = enqueue_rollouts(c, a, hc.tail(), hc.lead_dev());
     if (rc) return rc;
-    uint32_t cnt[4];
-    rc = stage_download(c, out, {cnt, out_gain, out_steps, out_draws, out_flags, out_boards}, dout);
+    rc = hc.finish();
     if (rc) return rc;
-    return cnt[2] ? bad_cells_error() : M3_OK;
+    return hc.lead_host()[2] ? bad_cells_error() : M3_OK;
 }
 
 // ---- env ------------------------------------------------------------------
@@ -782,25 +661,33 @@ int m3_env_create(m3_ctx* c, int64_t n, int num_moves, int env_goal, m3_env** ou
     e->goal = env_goal;
     const size_t bytes = n * (size_t)c->N;
     hipError_t err = hipSuccess;
-    auto alloc = [&](auto** p, size_t sz) {
-        if (err == hipSuccess) err = hipMalloc((void**)p, sz ? sz : 4);
+    auto alloc = [&](auto** p, size_t sz, bool zero = false) {
+        if (err == hipSuccess) err = env_alloc(e, p, sz, zero);
     };
-    alloc(&e->boards[0], bytes);
-    alloc(&e->boards[1], bytes);
-    alloc(&e->seeds, n * 4);
-    alloc(&e->flags, n * 4);
-    alloc(&e->draws, n * 4);
-    alloc(&e->legal, n * 4ull * c->AW);
-    alloc(&e->score, n * 4);
-    alloc(&e->moves, n * 4);
-    alloc(&e->next_action, n * 4);
-    alloc(&e->reward, n * 4);
-    alloc(&e->done, n);
-    alloc(&e->trunc, n);
-    alloc(&e->counters, 64 * 4 * MAX_SHARDS);
+    // every per-board field starts zeroed: a never-reset env reads back zeros, not stale device memory.
+    // The fills go to the context stream and are finished before the env is handed out. As hipMemset
+    // calls they ran on the null stream, which may return before the fill is done and which the
+    // non-blocking context and shard streams do not wait for: a fill could land after m3_env_reset's
+    // seed upload on the context stream, and the first boards of the env then reset from seed 0.
+    constexpr bool ZERO = true;
+    alloc(&e->boards[0], bytes, ZERO);
+    alloc(&e->boards[1], bytes, ZERO);
+    alloc(&e->seeds, n * 4, ZERO);
+    alloc(&e->flags, n * 4, ZERO);
+    alloc(&e->draws, n * 4, ZERO);
+    alloc(&e->legal, n * 4ull * c->AW, ZERO);
+    alloc(&e->score, n * 4, ZERO);
+    alloc(&e->moves, n * 4, ZERO);
+    alloc(&e->next_action, n * 4, ZERO);
+    alloc(&e->reward, n * 4, ZERO);
+    alloc(&e->done, n, ZERO);
+    alloc(&e->trunc, n, ZERO);
+    alloc(&e->slot, n, ZERO);
+    // (the counters too: m3_env_stats of an env that was loaded with m3_env_set and has not stepped
+    // yet -- rederive zeroes them at its first step -- read back whatever the allocation held)
+    alloc(&e->counters, 64 * 4 * MAX_SHARDS, ZERO);
     alloc(&e->ovf_list, n * 4);
     alloc(&e->packed, 2 * n * 4);
-    alloc(&e->slot, n);
     alloc(&e->ne_words, (size_t)NSLOT * n * 4ull * ((c->N + 3) / 4));
     alloc(&e->ne_first, (size_t)NSLOT * n * 4);
     alloc(&e->ne_legal, (size_t)NSLOT * n * 4ull * c->AW);
@@ -823,21 +710,7 @@ int m3_env_create(m3_ctx* c, int64_t n, int num_moves, int env_goal, m3_env** ou
     });
     for (hipEvent_t& ev : e->gev)
         if (err == hipSuccess) err = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    // every per-board field starts zeroed: a never-reset env reads back zeros, not stale device memory.
-    // The fills go to the context stream and are finished before the env is handed out. As hipMemset
-    // calls they ran on the null stream, which may return before the fill is done and which the
-    // non-blocking context and shard streams do not wait for: a fill could land after m3_env_reset's
-    // seed upload on the context stream, and the first boards of the env then reset from seed 0.
-    {
-        // (the counters too: m3_env_stats of an env that was loaded with m3_env_set and has not stepped
-        // yet -- rederive zeroes them at its first step -- read back whatever the allocation held)
-        void* zp[] = {e->boards[0], e->boards[1], e->seeds, e->flags, e->draws, e->legal, e->score, e->moves,
-                      e->next_action, e->reward, e->done, e->trunc, e->slot, e->counters};
-        size_t zb[] = {bytes, bytes, n * 4ull, n * 4ull, n * 4ull, n * 4ull * c->AW, n * 4ull, n * 4ull,
-                       n * 4ull, n * 4ull, (size_t)n, (size_t)n, (size_t)n, 64 * 4 * (size_t)MAX_SHARDS};
-        for (int i = 0; i < 14 && err == hipSuccess; ++i) err = hipMemsetAsync(zp[i], 0, zb[i], c->stream);
-        if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
-    }
+    if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
     if (err != hipSuccess) {
         m3_env_destroy(e);
         return set_err(M3_ERR_HIP, "env allocation (%lld boards): %s", (long long)n, hipGetErrorString(err));
@@ -899,16 +772,7 @@ int m3_env_destroy(m3_env* e) {
     if (e->ustream) (void)hipStreamDestroy(e->ustream);
     for (hipEvent_t ev : e->gev)
         if (ev) (void)hipEventDestroy(ev);
-    void* ptrs[] = {e->boards[0], e->boards[1], e->seeds, e->flags, e->draws, e->legal, e->score, e->moves,
-                    e->next_action, e->reward, e->done, e->trunc, e->actions[0], e->actions[1], e->counters,
-                    e->ovf_list,
-                    e->packed, e->gathered, e->slot, e->ne_words, e->ne_first, e->ne_legal, e->ne_flags,
-                    e->spill, e->m397, e->cont, e->defer, e->tab, e->look_act, e->look_list, e->look_cnt};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    for (int q = 0; q < PF_LAG; ++q)
-        for (void* p : {(void*)e->pf_list[q], (void*)e->pf_seed[q], (void*)e->pf_slot[q]})
-            if (p) (void)hipFree(p);
+    for (void* p : e->owned) (void)hipFree(p);
     if (e->comm) ncclCommDestroy(e->comm);
     for (hipEvent_t ev : e->tev) (void)hipEventDestroy(ev);
     delete e;
@@ -978,9 +842,7 @@ int m3_env_set_autoreset(m3_env* e, int enabled, uint32_t seed_stride) {
 
 int m3_env_step_device(m3_env* e, const int32_t* d_actions) {
     CHECK_ARG(e, "null env");
-    if (!e->ready)
-        return set_err(M3_ERR_STATE, "m3_env_step before m3_env_reset (or before m3_env_set of boards, seeds, "
-                                     "score, moves and next_action)");
+    if (!e->ready) return not_ready_error("m3_env_step");
     HIP_TRY(hipSetDevice(e->ctx->device));
     return with_shape(e->ctx->shape, [&](auto cf) {
         if (e->stale) {
@@ -999,9 +861,7 @@ int m3_env_step_device(m3_env* e, const int32_t* d_actions) {
 int m3_env_step(m3_env* e, const int32_t* actions) {
     CHECK_ARG(e, "null env");
     if (!actions) return m3_env_step_device(e, nullptr);
-    if (!e->ready)
-        return set_err(M3_ERR_STATE, "m3_env_step before m3_env_reset (or before m3_env_set of boards, seeds, "
-                                     "score, moves and next_action)");
+    if (!e->ready) return not_ready_error("m3_env_step");
     HIP_TRY(hipSetDevice(e->ctx->device));
     // a loaded env rederives (and restarts the step counter) before the upload buffer's parity is
     // chosen: the kernel of this step reads actions[steps & 1] of the counter it runs under
@@ -1012,7 +872,7 @@ int m3_env_step(m3_env* e, const int32_t* actions) {
         HIP_TRY(hipStreamCreateWithFlags(&e->ustream, hipStreamNonBlocking));
         for (int p = 0; p < 2; ++p) {
             HIP_TRY(hipEventCreateWithFlags(&e->upload_ev[p], hipEventDisableTiming));
-            HIP_TRY(hipMalloc(&e->actions[p], bytes));
+            HIP_TRY(env_alloc(e, &e->actions[p], bytes, false));
             HIP_TRY(hipHostMalloc(&e->hstage[p], bytes, hipHostMallocDefault));
         }
     }
@@ -1037,16 +897,14 @@ int m3_env_step(m3_env* e, const int32_t* actions) {
 // previous step's k_env_step / k_env_cont_grid / k_env_fix, ahead of whatever is enqueued next.
 int m3_env_lookahead(m3_env* e, int32_t* d_best_action, int32_t* d_best_reward, int32_t* d_values) {
     CHECK_ARG(e, "null env");
-    if (!e->ready)
-        return set_err(M3_ERR_STATE, "m3_env_lookahead before m3_env_reset (or before m3_env_set of boards, seeds, "
-                                     "score, moves and next_action)");
+    if (!e->ready) return not_ready_error("m3_env_lookahead");
     m3_ctx* c = e->ctx;
     HIP_TRY(hipSetDevice(c->device));
     int rc = ensure_fresh(e);
     if (rc) return rc;
     if (!e->look_list) {
-        HIP_TRY(hipMalloc(&e->look_list, e->n * 4));
-        HIP_TRY(hipMalloc(&e->look_cnt, MAX_SHARDS * 4));
+        HIP_TRY(env_alloc(e, &e->look_list, e->n * 4, false));
+        HIP_TRY(env_alloc(e, &e->look_cnt, MAX_SHARDS * 4, false));
     }
     for (int s = 0; s < (int)e->shards.size(); ++s) {
         m3_env::Shard& sh = e->shards[s];
@@ -1074,11 +932,9 @@ int m3_env_lookahead(m3_env* e, int32_t* d_best_action, int32_t* d_best_reward, 
 
 int m3_env_step_greedy(m3_env* e) {
     CHECK_ARG(e, "null env");
-    if (!e->ready)
-        return set_err(M3_ERR_STATE, "m3_env_step_greedy before m3_env_reset (or before m3_env_set of boards, "
-                                     "seeds, score, moves and next_action)");
+    if (!e->ready) return not_ready_error("m3_env_step_greedy");
     HIP_TRY(hipSetDevice(e->ctx->device));
-    if (!e->look_act) HIP_TRY(hipMalloc(&e->look_act, e->n * 4));
+    if (!e->look_act) HIP_TRY(env_alloc(e, &e->look_act, e->n * 4, false));
     // (each shard's step kernel follows its lookahead on the same stream, and the lookahead of the
     // next step follows the step: look_act needs no double buffer)
     int rc = m3_env_lookahead(e, e->look_act, nullptr, nullptr);
@@ -1208,18 +1064,18 @@ int m3_env_comm_init(m3_env* e, const uint8_t id[128], int nranks, int rank) {
     CHECK_ARG(e && id && nranks >= 1 && rank >= 0 && rank < nranks, "bad arguments");
     if (e->comm) return set_err(M3_ERR_STATE, "m3_env_comm_init: the env already has a communicator");
     HIP_TRY(hipSetDevice(e->ctx->device));
-    int32_t* g = nullptr;
-    HIP_TRY(hipMalloc(&g, (size_t)nranks * e->n * 4));
+    HIP_TRY(env_alloc(e, &e->gathered, (size_t)nranks * e->n * 4, false));
     ncclUniqueId uid;
     memcpy(&uid, id, 128);
     ncclComm_t comm = nullptr;
     const ncclResult_t r = ncclCommInitRank(&comm, nranks, uid, rank);
-    if (r != ncclSuccess) {
-        (void)hipFree(g);
+    if (r != ncclSuccess) {  // no communicator, no buffer: take back the allocation just recorded
+        e->owned.pop_back();
+        (void)hipFree(e->gathered);
+        e->gathered = nullptr;
         return set_err(M3_ERR_RCCL, "ncclCommInitRank: %s", ncclGetErrorString(r));
     }
     e->comm = comm;
-    e->gathered = g;
     e->nranks = nranks;
     e->rank = rank;
     return M3_OK;

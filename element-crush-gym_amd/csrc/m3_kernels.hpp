@@ -2146,6 +2146,8 @@ struct m3_env {
     // on request otherwise (20 B per board and step fewer writes)
     bool legal_eager = false;
     bool stale = false;  // fields were loaded with m3_env_set: rederive() before the next step
+    // every device allocation below, as env_alloc (m3_api.hip) made it: m3_env_destroy frees these
+    std::vector<void*> owned;
     int8_t* boards[2] = {nullptr, nullptr};
     int cur = 0;
     uint32_t *seeds = nullptr, *flags = nullptr, *draws = nullptr, *legal = nullptr;

@@ -497,3 +497,93 @@ def test_abi_rejects_bad_cells_on_device(ctxs):
     b[257, 40] = 3  # a valid value: both calls succeed again on the same context
     _native.check(L.m3_apply_actions(c.handle, n, P(b), P(seeds), P(na), P(fa), *[P(o) for o in outs], None, None))
     _native.check(L.m3_rollouts(c.handle, n, P(b), P(seeds), P(na), P(seeds), *[P(o) for o in routs], None))
+
+
+def _host_buffer_calls(ctx, seeds):
+    """Every host-buffer call with every optional output, on the boards of `seeds`: {name: array}."""
+    out = {}
+    boards, out["init.draws"], first, out["init.flags"] = ctx.init_boards(seeds, flags=True)
+    out["init.boards"], out["init.first"] = boards, first
+    for k, v in ctx.apply_actions(boards, seeds, 20, first, legal=True, next_action=True).items():
+        out["apply." + k] = v
+    out["legal"] = ctx.legal_bits(boards)
+    for k, v in ctx.lookahead(boards, seeds, 20, values=True).items():
+        out["look." + k] = v
+    for k, v in ctx.rollouts(boards, seeds, 20, seeds + np.uint32(6), final_boards=True).items():
+        out["roll." + k] = v
+    return out
+
+
+@pytest.mark.parametrize("shape", [(9, 9, 6), (8, 8, 5)], ids=["9x9x6", "8x8x5"])
+def test_host_buffer_calls_same_on_both_routes(shape):
+    """m3_init_boards_ex, m3_apply_actions, m3_legal_actions and m3_lookahead take the zero-copy route
+    up to 256 boards and the staged route above: on one fresh context (its buffers grow from empty)
+    the calls at n = 1, 256 (the largest zero-copy call), 257 (the smallest staged call) and 1 again
+    return the same rows in every output, and rows 0, 128, 255 and 256 are the oracle's. m3_rollouts
+    is staged at every n: its rows agree between the sizes."""
+    import lookahead_ref as ref
+
+    seeds = np.arange(1, 258, dtype=np.uint32)
+    ctx = _native.Context(*shape)
+    try:
+        one, zc, staged, again = (_host_buffer_calls(ctx, seeds[:n]) for n in (1, 256, 257, 1))
+    finally:
+        ctx.close()
+    assert set(staged) >= {"init.flags", "apply.legal", "apply.next_action", "look.values", "roll.final"}
+    for k, v in staged.items():
+        assert len(v) == 257 and len(zc[k]) == 256, k
+        assert (zc[k] == v[:256]).all(), k
+        assert (one[k] == v[:1]).all() and (again[k] == v[:1]).all(), k
+    o = Oracle(*shape)
+    rows = [0, 128, 255, 256]
+    want = ref.oracle_lookahead(shape, staged["init.boards"][rows], seeds[rows], 20)
+    ref.assert_equal({k[5:]: v[rows] for k, v in staged.items() if k.startswith("look.")}, want, shape)
+    for i in rows:
+        s = int(seeds[i])
+        b, d = o.init_board(s)
+        assert (staged["init.boards"][i] == b).all() and staged["init.draws"][i] == d, i
+        assert staged["init.first"][i] == o.random_action(b, s)[0], i
+        assert np.array_equal(np.flatnonzero(unpack(staged["legal"][i], o.A)), o.legal_actions(b)), i
+        nb, r, dr, _, nxt, _ = o.apply_action_next(b, s, int(staged["init.first"][i]), 20)
+        assert (staged["apply.boards"][i] == nb).all(), i
+        assert (staged["apply.reward"][i], staged["apply.draws"][i], staged["apply.next_action"][i]) == (r, dr, nxt), i
+        assert np.array_equal(np.flatnonzero(unpack(staged["apply.legal"][i], o.A)), o.legal_actions(nb)), i
+
+
+def test_abi_bad_cells_zero_copy_and_recovery():
+    """test_abi_rejects_bad_cells_on_device on the zero-copy route (3 boards): m3_apply_actions and
+    m3_lookahead reject the negative cell, and with the cell restored both succeed on the same
+    context -- the pinned bad-cell word and the device's overflow word were left clean -- with
+    m3_apply_actions' outputs the oracle's for all three boards."""
+    c = _native.Context(9, 9, 6)
+    n = 3
+    seeds = np.arange(1, n + 1, dtype=np.uint32)
+    b, _, fa = c.init_boards(seeds)
+    b = np.ascontiguousarray(b.reshape(n, -1))
+    na = np.full(n, 20, np.int32)
+    fa = np.ascontiguousarray(fa, dtype=np.int32)
+    outs = [np.empty(n * 81, np.int8)] + [np.empty(n, np.int32) for _ in range(3)]
+    louts = [np.empty(n, np.int32) for _ in range(2)]  # every buffer outlives the calls
+    P = _native.ptr
+    L = _native.lib()
+
+    def apply():
+        return L.m3_apply_actions(c.handle, n, P(b), P(seeds), P(na), P(fa), *[P(o) for o in outs], None, None)
+
+    def look():
+        return L.m3_lookahead(c.handle, n, P(b), P(seeds), P(na), *[P(o) for o in louts], None, None, None)
+
+    try:
+        good = b[2, 40]
+        b[2, 40] = -3
+        assert apply() == -1 and b"outside [0, 127]" in L.m3_last_error()
+        assert look() == -1 and b"outside [0, 127]" in L.m3_last_error()
+        b[2, 40] = good
+        _native.check(apply())
+        _native.check(look())
+    finally:
+        c.close()
+    o = Oracle()
+    for i in range(n):
+        ob, orr, od, _ = o.apply_action(b[i].reshape(9, 9).astype(np.int32), int(seeds[i]), int(fa[i]))
+        assert (outs[0].reshape(n, 81)[i] == ob.reshape(-1)).all() and outs[1][i] == orr and outs[2][i] == od, i

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-call latency of the batch-1 facade path (unchanged mctslib / samplerTasks callers).
 
-    python3 tools/latency.py [--calls 300] [--out gpurun_out/latency.json]
+    python3 tools/latency.py [--calls 300] [--boards 1] [--out latency.json]
 
 The reference's MCTS expands and rolls out one node at a time
 (mctslib/standard/mcts.py:14-19,31-42): every BoardV2.apply_action /
@@ -11,7 +11,8 @@ legal_actions is one call on one board. Times, on the MI355X box, the median
     numpy global-RNG replay), and the bare C-ABI call for one board;
   * BoardV2.legal_actions (uncached: a fresh board each call) and m3_legal_actions;
   * BoardV2(20, cfg) (reset, m3_init_boards);
-  * MCTS.rollout of one state (m3_rollouts, 19 moves);
+  * MCTS.rollout of one state (m3_rollouts, 19 moves) and BoardV2.greedy_action's lookahead (m3_lookahead);
+the bare C-ABI rows (abi_*) on --boards N boards per call (default 1; above 256 the staged route);
 beside the reference's own per-call CPU times measured in the build container
 (apply_action 0.74 ms, legal_actions 0.34 ms, __init__ 0.35 ms at 9x9x6).
 """
@@ -48,25 +49,31 @@ def timeit(fn, calls, warm=20):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=300)
+    ap.add_argument("--boards", type=int, default=1, help="boards per call of the abi_* rows")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     cfg = BoardConfig(seed=12345)
     b0 = BoardV2(20, cfg)
     ctx = _native.context(9, 9, 6)
-    seeds = np.array([cfg.seed], np.uint32)
-    boards = b0.array.astype(np.int8)[None]
     legal = b0.legal_actions
     act = int(legal[0])
+    # the abi_* rows: N boards per call (N = 1: the facade's own call; above 256 the staged route)
+    N = a.boards
+    seeds = np.full(N, cfg.seed, np.uint32)
+    boards = np.repeat(b0.array.astype(np.int8)[None], N, axis=0)
+    rseeds = np.full(N, 7, np.uint32)
     res = {}
     res["facade_apply_action"] = timeit(lambda: b0.apply_action(act), a.calls)
-    res["abi_apply_actions_n1"] = timeit(lambda: ctx.apply_actions(boards, seeds, 20, act), a.calls)
+    res[f"abi_apply_actions_n{N}"] = timeit(lambda: ctx.apply_actions(boards, seeds, 20, act), a.calls)
     fresh = [BoardV2(20, cfg, b0.array.copy()) for _ in range(a.calls + 20)]
     it = iter(fresh)
     res["facade_legal_actions_uncached"] = timeit(lambda: next(it).legal_actions, a.calls)
-    res["abi_legal_actions_n1"] = timeit(lambda: ctx.legal_bits(boards), a.calls)
+    res[f"abi_legal_actions_n{N}"] = timeit(lambda: ctx.legal_bits(boards), a.calls)
     res["facade_init"] = timeit(lambda: BoardV2(20, cfg), a.calls)
-    res["abi_rollouts_n1"] = timeit(lambda: ctx.rollouts(boards, seeds, 19, np.array([7], np.uint32)), a.calls)
-    out = {"what": "per-call wall time, batch 1, 9x9x6, MI355X (tools/latency.py)",
+    res[f"abi_rollouts_n{N}"] = timeit(lambda: ctx.rollouts(boards, seeds, 19, rseeds), a.calls)
+    res[f"abi_lookahead_n{N}"] = timeit(lambda: ctx.lookahead(boards, seeds, 20), a.calls)
+    out = {"what": "per-call wall time, batch 1 (abi_* rows: --boards), 9x9x6, MI355X (tools/latency.py)",
+           "boards": N,
            "reference_python_ms": REFERENCE_MS, "results": res,
            "vs_reference": {"apply_action": REFERENCE_MS["apply_action"] * 1e3 / res["facade_apply_action"]["median_us"],
                             "legal_actions": REFERENCE_MS["legal_actions"] * 1e3
