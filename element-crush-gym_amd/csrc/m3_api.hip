@@ -1,5 +1,6 @@
 // m3_api.hip -- the C ABI of include/m3.h (kernels and launchers: m3_kernels.hpp).
 #include "m3_kernels.hpp"
+#include "m3_search.hpp"
 
 #include <string>
 
@@ -1231,6 +1232,322 @@ int m3_env_step_kernel_ms(m3_env* e, float* out_ms, int max_n, int* out_n) {
     for (int i = 0; i < n; ++i) HIP_TRY(hipEventElapsedTime(&out_ms[i], e->tev[3 * i], e->tev[3 * i + 1]));
     *out_n = n;
     return M3_OK;
+}
+
+}  // extern "C"
+
+// ---- device-resident MCTS trees (m3_search.hpp: the tree kernels) -------------
+struct m3_search {
+    m3_ctx* ctx = nullptr;
+    int64_t n = 0;
+    int32_t cap = 0;
+    bool ready = false;
+    int64_t used = 0;  // nodes below the root ever attached, per game at most (m3s::search_run_fits)
+    m3s::SearchRound R{};
+    uint32_t* seeds = nullptr;  // [n] cfg.seed of each game
+    // the rest of the apply and rollout launches' outputs
+    int8_t* out_boards = nullptr;
+    int32_t* out_reward = nullptr;
+    uint32_t *out_draws = nullptr, *out_flags = nullptr, *out_legal = nullptr, *apply_list = nullptr;
+    int32_t *ro_gain = nullptr, *ro_steps = nullptr;
+    uint32_t *ro_draws = nullptr, *ro_flags = nullptr;
+    char* ro_tail = nullptr;       // rollout_tail_bytes: the exact pass's list and the spill pool
+    uint32_t* counters = nullptr;  // [0] the apply launch's overflow count, [4..7] the rollout launch's counters
+    int32_t* keep_best = nullptr;  // [n] best_action of the last m3_search_result
+    uint64_t* stats = nullptr;
+    hipEvent_t up_ev = nullptr;    // the rollout seeds of a run have left the pinned staging
+    std::vector<void*> owned;
+};
+
+namespace {
+
+template <class T>
+hipError_t search_alloc(m3_search* s, T** field, size_t bytes) {
+    hipError_t err = hipMalloc((void**)field, bytes ? bytes : 4);
+    if (err == hipSuccess) s->owned.push_back(*field);
+    return err;
+}
+
+// One simulation round on the context stream (rollout = false: the constructor's expansion only).
+int enqueue_search_round(m3_search* s, const uint32_t* d_rseeds, bool rollout) {
+    m3_ctx* c = s->ctx;
+    HIP_TRY(m3s::launch_search_select(c->stream, s->R));
+    ApplyArgs a{};
+    a.shape = c->sdesc;
+    a.n = s->n;
+    a.boards = s->R.row_boards;
+    a.seeds = s->seeds;
+    a.n_actions = s->R.row_na;
+    a.actions = s->R.T.action;
+    a.out_boards = s->out_boards;
+    a.reward = s->out_reward;
+    a.draws = s->out_draws;
+    a.flags = s->out_flags;
+    a.legal = s->out_legal;
+    a.ovf_count = s->counters;
+    a.ovf_list = s->apply_list;
+    int rc = with_shape(c->shape, [&](auto cf) { return launch_apply<decltype(cf)>(c, a); });
+    if (rc) return rc;
+    HIP_TRY(m3s::launch_search_attach(c->stream, s->R));
+    if (!rollout) return M3_OK;
+    RolloutArgs r{};
+    r.n = s->n;
+    r.boards = s->R.ro_boards;
+    r.seeds = s->seeds;
+    r.n_actions = s->R.ro_na;
+    r.rseeds = d_rseeds;
+    r.gain = s->ro_gain;
+    r.steps = s->ro_steps;
+    r.draws = s->ro_draws;
+    r.flags = s->ro_flags;
+    rc = enqueue_rollouts(c, r, s->ro_tail, s->counters + 4);
+    if (rc) return rc;
+    HIP_TRY(m3s::launch_search_backup(c->stream, s->R));
+    return M3_OK;
+}
+
+int search_not_ready(const char* entry) { return set_err(M3_ERR_STATE, "%s before m3_search_set_roots", entry); }
+
+}  // namespace
+
+extern "C" {
+
+int m3_search_log_table(int32_t n, double* out) {
+    CHECK_ARG(n >= 0 && (n == 0 || out), "bad arguments");
+    std::vector<double> tab((size_t)n + 1);
+    m3s::search_log_table(n, tab.data());
+    for (int32_t v = 1; v <= n; ++v) out[v - 1] = tab[v];
+    return M3_OK;
+}
+
+int m3_search_create(m3_ctx* c, int64_t n, int32_t node_capacity, m3_search** out) {
+    CHECK_ARG(c && out && n > 0 && node_capacity >= 2, "bad arguments");
+    CHECK_ARG(n < (int64_t)1 << 31, "n too large");
+    *out = nullptr;
+    int rc = check_ids_on_board(c);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    m3_search* s = new m3_search;
+    s->ctx = c;
+    s->n = n;
+    s->cap = node_capacity;
+    m3s::STree& T = s->R.T;
+    T.n = n;
+    T.cap = node_capacity;
+    T.N = c->N;
+    T.AW = c->AW;
+    T.A = c->A;
+    const size_t nodes = (size_t)n * (size_t)node_capacity, bytes = (size_t)n * c->N, aw = (size_t)n * 4 * c->AW;
+    hipError_t err = hipSuccess;
+    auto alloc = [&](auto** p, size_t sz) {
+        if (err == hipSuccess) err = search_alloc(s, p, sz);
+    };
+    alloc(&T.hot, nodes * sizeof(m3s::SNodeHot));
+    alloc(&T.link, nodes * sizeof(m3s::SNodeLink));
+    alloc(&T.untried, nodes * 4 * c->AW);
+    alloc(&T.boards, nodes * c->N);
+    alloc(&T.root, n * 4);
+    alloc(&T.used, n * 4);
+    alloc(&T.leaf, n * 4);
+    alloc(&T.expanded, n * 4);
+    alloc(&T.action, n * 4);
+    alloc(&T.gflags, n * 4);
+    double* log_tab = nullptr;
+    alloc(&log_tab, ((size_t)node_capacity + 1) * 8);
+    T.log_tab = log_tab;
+    alloc(&s->R.row_boards, bytes);
+    alloc(&s->R.row_na, n * 4);
+    alloc(&s->R.ro_boards, bytes);
+    alloc(&s->R.ro_na, n * 4);
+    alloc(&s->seeds, n * 4);
+    alloc(&s->out_boards, bytes);
+    alloc(&s->out_reward, n * 4);
+    alloc(&s->out_draws, n * 4);
+    alloc(&s->out_flags, n * 4);
+    alloc(&s->out_legal, aw);
+    alloc(&s->apply_list, n * 4);
+    alloc(&s->ro_gain, n * 4);
+    alloc(&s->ro_steps, n * 4);
+    alloc(&s->ro_draws, n * 4);
+    alloc(&s->ro_flags, n * 4);
+    alloc(&s->ro_tail, rollout_tail_bytes(c->shape, n));
+    alloc(&s->counters, 32);
+    alloc(&s->keep_best, n * 4);
+    alloc(&s->stats, 32);
+    s->R.out_boards = s->out_boards;
+    s->R.out_reward = s->out_reward;
+    s->R.out_flags = s->out_flags;
+    s->R.out_legal = s->out_legal;
+    s->R.ro_gain = s->ro_gain;
+    s->R.ro_flags = s->ro_flags;
+    s->R.apply_ovf = s->counters;
+    s->R.ro_counters = s->counters + 4;
+    s->R.stats = s->stats;
+    std::vector<double> tab((size_t)node_capacity + 1);
+    m3s::search_log_table(node_capacity, tab.data());  // log on the host only (m3_search_core.hpp)
+    if (err == hipSuccess) err = hipEventCreateWithFlags(&s->up_ev, hipEventDisableTiming);
+    if (err == hipSuccess) err = hipMemcpyAsync(log_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream);
+    if (err == hipSuccess) err = hipMemsetAsync(s->counters, 0, 32, c->stream);
+    if (err == hipSuccess) err = hipMemsetAsync(s->stats, 0, 32, c->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
+    if (err != hipSuccess) {
+        m3_search_destroy(s);
+        return set_err(M3_ERR_HIP, "search allocation (%lld games x %d nodes): %s", (long long)n, node_capacity,
+                       hipGetErrorString(err));
+    }
+    *out = s;
+    return M3_OK;
+}
+
+int m3_search_destroy(m3_search* s) {
+    if (!s) return M3_OK;
+    (void)hipSetDevice(s->ctx->device);
+    (void)hipStreamSynchronize(s->ctx->stream);
+    for (void* p : s->owned) (void)hipFree(p);
+    if (s->up_ev) (void)hipEventDestroy(s->up_ev);
+    delete s;
+    return M3_OK;
+}
+
+int m3_search_set_roots(m3_search* s, const int8_t* boards, const uint32_t* seeds, const int32_t* n_actions,
+                        const int32_t* rewards) {
+    CHECK_ARG(s && boards && seeds && n_actions && rewards, "bad arguments");
+    m3_ctx* c = s->ctx;
+    const int64_t n = s->n;
+    for (size_t i = 0, e = (size_t)n * c->N; i < e; ++i)
+        if (boards[i] < 0) return bad_cells_error();
+    HIP_TRY(hipSetDevice(c->device));
+    s->ready = false;
+    HostCall hc(c);
+    const int i_b = hc.input(boards, n * (size_t)c->N), i_s = hc.input(seeds, n * 4ull),
+              i_na = hc.input(n_actions, n * 4ull), i_r = hc.input(rewards, n * 4ull);
+    int rc = hc.begin(false, 16, 0);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(s->seeds, hc.dev<const uint32_t>(i_s), n * 4ull, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(s->stats, 0, 32, c->stream));
+    rc = with_shape(c->shape, [&](auto cf) {
+        return launch_legal<decltype(cf)>(c, n, hc.dev<const int8_t>(i_b), s->out_legal);
+    });
+    if (rc) return rc;
+    HIP_TRY(m3s::launch_search_init(c->stream, s->R.T, hc.dev<const int8_t>(i_b), hc.dev<const int32_t>(i_na),
+                                    hc.dev<const int32_t>(i_r), s->out_legal));
+    rc = enqueue_search_round(s, nullptr, false);  // MCTS.__init__'s one expansion (abc/mcts.py:82)
+    if (rc) return rc;
+    rc = hc.finish();
+    if (rc) return rc;
+    s->used = 1;
+    s->ready = true;
+    return M3_OK;
+}
+
+int m3_search_run(m3_search* s, int32_t simulations, const uint32_t* rollout_seeds) {
+    CHECK_ARG(s && simulations >= 0 && (simulations == 0 || rollout_seeds), "bad arguments");
+    if (!s->ready) return search_not_ready("m3_search_run");
+    if (!m3s::search_run_fits(s->used, simulations, s->cap))  // before anything is enqueued
+        return set_err(M3_ERR_CAP, "%d simulations on trees of up to %lld nodes do not fit node_capacity %d",
+                       simulations, (long long)s->used + 1, s->cap);
+    if (simulations == 0) return M3_OK;
+    m3_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    HostCall hc(c);
+    const int i_rs = hc.input(rollout_seeds, (size_t)simulations * s->n * 4ull);
+    int rc = hc.begin(false, 0, 0);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(s->up_ev, c->stream));
+    s->used += simulations;
+    const uint32_t* d_rs = hc.dev<const uint32_t>(i_rs);
+    for (int32_t k = 0; k < simulations && rc == M3_OK; ++k) rc = enqueue_search_round(s, d_rs + (size_t)k * s->n, true);
+    // the seeds have left the pinned staging (the next host-buffer call may fill it); the kernels run on
+    HIP_TRY(hipEventSynchronize(s->up_ev));
+    return rc;
+}
+
+int m3_search_result(m3_search* s, int32_t* best_action, int32_t* value, int32_t* root_visits, int32_t* n_children,
+                     int32_t* child_action, int32_t* child_visits, int64_t* child_reward, uint32_t* flags) {
+    CHECK_ARG(s, "null search");
+    if (!s->ready) return search_not_ready("m3_search_result");
+    m3_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = (size_t)s->n, na = n * c->A;
+    HostCall hc(c);
+    const int o_a = hc.output(best_action, n * 4), o_v = hc.output(value, n * 4), o_rv = hc.output(root_visits, n * 4),
+              o_nc = hc.output(n_children, n * 4), o_ca = hc.output(child_action, na * 4),
+              o_cv = hc.output(child_visits, na * 4), o_cr = hc.output(child_reward, na * 8),
+              o_f = hc.output(flags, n * 4);
+    int rc = hc.begin(false, 16, 0);
+    if (rc) return rc;
+    m3s::SResult r{hc.dev<int32_t>(o_a),  hc.dev<int32_t>(o_v),  hc.dev<int32_t>(o_rv), hc.dev<int32_t>(o_nc),
+                   hc.dev<int32_t>(o_ca), hc.dev<int32_t>(o_cv), hc.dev<int64_t>(o_cr), hc.dev<uint32_t>(o_f)};
+    HIP_TRY(m3s::launch_search_finish(c->stream, s->R.T, r, s->keep_best, s->stats));
+    return hc.finish();
+}
+
+int m3_search_advance(m3_search* s, const int32_t* actions, int8_t* out_boards, int32_t* out_rewards,
+                      int32_t* out_n_actions, uint32_t* out_legal_bits) {
+    CHECK_ARG(s, "null search");
+    if (!s->ready) return search_not_ready("m3_search_advance");
+    m3_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = (size_t)s->n;
+    std::vector<uint32_t> fl(n);
+    HostCall hc(c);
+    const int i_a = actions ? hc.input(actions, n * 4) : -1;
+    const int o_b = hc.output(out_boards, n * c->N), o_r = hc.output(out_rewards, n * 4),
+              o_na = hc.output(out_n_actions, n * 4), o_l = hc.output(out_legal_bits, n * 4 * c->AW),
+              o_f = hc.output(fl.data(), n * 4);
+    int rc = hc.begin(false, 16, 0);
+    if (rc) return rc;
+    // (outputs the caller does not want land in the round's row buffers, rewritten by the next round)
+    int8_t* d_b = out_boards ? hc.dev<int8_t>(o_b) : s->R.row_boards;
+    HIP_TRY(m3s::launch_search_advance(c->stream, s->R.T, actions ? hc.dev<const int32_t>(i_a) : s->keep_best, d_b,
+                                       out_rewards ? hc.dev<int32_t>(o_r) : s->out_reward,
+                                       out_n_actions ? hc.dev<int32_t>(o_na) : s->R.row_na, hc.dev<uint32_t>(o_f)));
+    if (out_legal_bits) {
+        rc = with_shape(c->shape, [&](auto cf) { return launch_legal<decltype(cf)>(c, s->n, d_b, hc.dev<uint32_t>(o_l)); });
+        if (rc) return rc;
+    }
+    rc = hc.finish();
+    if (rc) return rc;
+    int64_t bad = 0;
+    for (uint32_t f : fl) bad += (f & M3_FLAG_BAD_ACTION) != 0;
+    if (bad)
+        return set_err(M3_ERR_INVALID, "%lld of %lld games: the action has no expanded child of the root (their roots "
+                       "stay; the outputs hold the current roots)", (long long)bad, (long long)n);
+    return M3_OK;
+}
+
+int m3_search_stats(m3_search* s, uint64_t out[4]) {
+    CHECK_ARG(s && out, "bad arguments");
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    HIP_TRY(hipMemcpyAsync(out, s->stats, 32, hipMemcpyDeviceToHost, s->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+    return M3_OK;
+}
+
+int m3_search_ucb1(m3_ctx* c, int64_t n, const int64_t* reward_sum, const int32_t* visits, const int32_t* parent_visits,
+                   const double* cw, double* out) {
+    CHECK_ARG(c && n >= 0, "bad arguments");
+    if (n == 0) return M3_OK;
+    CHECK_ARG(reward_sum && visits && parent_visits && cw && out, "null buffer");
+    int32_t top = 1;
+    for (int64_t i = 0; i < n; ++i) {
+        CHECK_ARG(visits[i] >= 0 && parent_visits[i] >= 1 && parent_visits[i] <= 1 << 24, "visits out of range");
+        top = std::max(top, parent_visits[i]);
+    }
+    std::vector<double> tab((size_t)top + 1);
+    m3s::search_log_table(top, tab.data());
+    HIP_TRY(hipSetDevice(c->device));
+    HostCall hc(c);
+    const int i_r = hc.input(reward_sum, n * 8ull), i_v = hc.input(visits, n * 4ull),
+              i_p = hc.input(parent_visits, n * 4ull), i_c = hc.input(cw, n * 8ull),
+              i_t = hc.input(tab.data(), tab.size() * 8);
+    const int o = hc.output(out, n * 8ull);
+    int rc = hc.begin(false, 0, 0);
+    if (rc) return rc;
+    HIP_TRY(m3s::launch_search_ucb1(c->stream, n, hc.dev<const int64_t>(i_r), hc.dev<const int32_t>(i_v),
+                                    hc.dev<const int32_t>(i_p), hc.dev<const double>(i_c), hc.dev<const double>(i_t),
+                                    hc.dev<double>(o)));
+    return hc.finish();
 }
 
 }  // extern "C"

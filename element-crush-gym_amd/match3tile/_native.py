@@ -42,6 +42,8 @@ EXPORTS = [
     "m3_comm_unique_id", "m3_env_comm_init", "m3_env_comm_size", "m3_env_gather", "m3_env_gather_device", "m3_env_debug_stall",
     "m3_env_stats", "m3_ctx_timer", "m3_env_timing",
     "m3_env_kernel_ms", "m3_env_step_kernel_ms",
+    "m3_search_create", "m3_search_destroy", "m3_search_log_table", "m3_search_set_roots", "m3_search_run",
+    "m3_search_result", "m3_search_advance", "m3_search_stats", "m3_search_ucb1",
 ]
 
 
@@ -112,6 +114,15 @@ def lib():
             "m3_env_timing": ([vp, i32], i32),
             "m3_env_kernel_ms": ([vp, vp, i32, vp], i32),
             "m3_env_step_kernel_ms": ([vp, vp, i32, vp], i32),
+            "m3_search_create": ([vp, i64, i32, vp], i32),
+            "m3_search_destroy": ([vp], i32),
+            "m3_search_log_table": ([i32, vp], i32),
+            "m3_search_set_roots": ([vp, vp, vp, vp, vp], i32),
+            "m3_search_run": ([vp, i32, vp], i32),
+            "m3_search_result": ([vp] * 9, i32),
+            "m3_search_advance": ([vp] * 6, i32),
+            "m3_search_stats": ([vp, vp], i32),
+            "m3_search_ucb1": ([vp, i64] + [vp] * 5, i32),
         }
         for name, (args, res) in sig.items():
             fn = getattr(L, name, None)  # (an older A/B build may lack newer entry points;

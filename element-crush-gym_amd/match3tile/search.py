@@ -1,0 +1,168 @@
+"""Device-resident MCTS: the search trees of many games in GPU memory, searched in lockstep.
+
+``match3tile.mcts.search_lockstep`` keeps every tree in Python: a simulation round walks each game's
+tree on the host, expands one node per game with a batch-1 ``apply_action`` and makes one blocking
+rollout call. ``DeviceSearch`` holds the trees in device memory (``m3_search_*``, include/m3.h): a
+round is selection, the expansions' ``apply_action``, the attach, the rollouts and the backup as five
+launches for all games at once, and a whole ``__call__`` -- ``simulations`` rounds -- is enqueued
+without a host round trip.
+
+The search is the reference's (mctslib/abc/mcts.py:71-128, standard/mcts.py), node for node: expansion
+order, UCB1 with the node's ``n_actions`` as the exploration weight, evaluated bit for bit as CPython
+evaluates it, one ``random.randint(0, 2**31 - 1)`` rollout seed per simulation from each game's own
+generator, root re-use between calls. So game g returns what ``MCTS(states[g], c, simulations,
+rng=rngs[g])()`` returns. (The reference's ``exploration_weight`` argument is not read by its
+selection, abc/mcts.py:96, and has no counterpart here.)
+
+``leaf_rollouts > 1`` and ``deterministic=True`` stay on the host path (``match3tile.mcts.MCTS``).
+
+numpy's global RNG: the reference leaves it where the last rollout's last ``apply_action`` left it.
+After a device search its state is unspecified (nothing is replayed into it); nothing in
+``dataset.play_games`` reads it.
+
+Memory: ``node_capacity`` node slots per game, 16 + 32 + 4 * ceil(A / 32) + rows * columns bytes each
+(9x9x6: 149 bytes, so the default ``2 + n_actions * simulations`` slots of a 20-move, 256-simulation
+game are 763 KB per game, 3.1 GB for 4,096 games). Slots are not reclaimed on re-rooting.
+"""
+from __future__ import annotations
+
+import ctypes
+import random
+from typing import List, Optional, Sequence
+
+import numpy as np
+
+from . import _native
+from .boardv2 import BoardV2
+from .mcts import SEED_BOUND
+
+_CAPS = _native.FLAG_SHUFFLE_CAP | _native.FLAG_CASCADE_CAP
+
+
+class DeviceSearch:
+    """``DeviceSearch(states, simulations, rngs=None, node_capacity=None)``: one tree per BoardV2 state.
+
+    All states share a board shape and ``simulations``. ``rngs[g]`` (default: the ``random`` module for
+    every game, drawn game by game) is the source of game g's rollout seeds. ``node_capacity``
+    defaults to ``2 + max(n_actions) * simulations``: enough for one ``__call__`` per remaining move."""
+
+    def __init__(self, states: Sequence, simulations: int, rngs: Optional[Sequence] = None,
+                 node_capacity: Optional[int] = None):
+        states = list(states)
+        if not states:
+            raise ValueError("DeviceSearch needs at least one state")
+        cfg = states[0].cfg
+        shape = (cfg.rows, cfg.columns, cfg.types)
+        if any((s.cfg.rows, s.cfg.columns, s.cfg.types) != shape for s in states):
+            raise ValueError("DeviceSearch needs states of one board shape")
+        if rngs is not None and len(rngs) != len(states):
+            raise ValueError("one rng per state")
+        self._ctx = _native.context(*shape)
+        self._cfgs = [s.cfg for s in states]
+        self._rngs = [random] * len(states) if rngs is None else list(rngs)
+        self.simulations = int(simulations)
+        self.n = len(states)
+        if node_capacity is None:
+            node_capacity = 2 + max(1, max(s.n_actions for s in states)) * self.simulations
+        self.node_capacity = int(node_capacity)
+        h = ctypes.c_void_p()
+        _native.check(_native.lib().m3_search_create(self._ctx.handle, self.n, self.node_capacity, ctypes.byref(h)))
+        self._h = h
+        boards = self._ctx._boards(np.stack([np.asarray(s.array) for s in states]))
+        seeds = np.array([int(s.cfg.seed) & 0xFFFFFFFF for s in states], dtype=np.uint32)
+        na = np.array([s.n_actions for s in states], dtype=np.int32)
+        rew = np.array([int(s.reward) for s in states], dtype=np.int32)
+        with self._ctx._lock:
+            _native.check(_native.lib().m3_search_set_roots(self._h, _native.ptr(boards), _native.ptr(seeds),
+                                                            _native.ptr(na), _native.ptr(rew)))
+        self._states = [s.clone() for s in states]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _native.lib().m3_search_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- the raw calls -------------------------------------------------------------
+    def run(self, rollout_seeds) -> None:
+        """Enqueue len(rollout_seeds) rounds; rollout_seeds [rounds][n]. Does not wait for the kernels.
+        Raises M3Error (M3_ERR_CAP) if the rounds do not fit node_capacity; nothing is run then."""
+        rs = np.ascontiguousarray(rollout_seeds, dtype=np.uint32).reshape(-1, self.n)
+        with self._ctx._lock:
+            _native.check(_native.lib().m3_search_run(self._h, len(rs), _native.ptr(rs)))
+
+    def result(self, children: bool = True) -> dict:
+        """m3_search_result: best_action, value, root_visits, n_children, flags and, with children, the
+        root's child_action / child_visits / child_reward [n, A] in expansion order. Blocks."""
+        n, A = self.n, self._ctx.A
+        out = dict(best_action=np.empty(n, np.int32), value=np.empty(n, np.int32), root_visits=np.empty(n, np.int32),
+                   n_children=np.empty(n, np.int32), child_action=np.empty((n, A), np.int32) if children else None,
+                   child_visits=np.empty((n, A), np.int32), child_reward=np.empty((n, A), np.int64) if children else None,
+                   flags=np.empty(n, np.uint32))
+        order = ("best_action", "value", "root_visits", "n_children", "child_action", "child_visits", "child_reward",
+                 "flags")
+        with self._ctx._lock:
+            _native.check(_native.lib().m3_search_result(self._h, *[_native.ptr(out[k]) for k in order]))
+        return out
+
+    def stats(self) -> dict:
+        out = np.zeros(4, np.uint64)
+        with self._ctx._lock:
+            _native.check(_native.lib().m3_search_stats(self._h, _native.ptr(out)))
+        return dict(nodes_used=int(out[0]), rounds=int(out[1]), apply_exact=int(out[2]), rollout_exact=int(out[3]))
+
+    def advance(self, actions=None) -> List[BoardV2]:
+        """Re-root every game at the child ``actions[g]`` leads to (None: the last result's best
+        action) and return the new roots. The subtrees keep their statistics."""
+        n, ctx = self.n, self._ctx
+        act = None if actions is None else np.ascontiguousarray(actions, dtype=np.int32).reshape(n)
+        boards = np.empty((n, ctx.N), np.int8)
+        rew, na = np.empty(n, np.int32), np.empty(n, np.int32)
+        legal = np.empty((n, ctx.words), np.uint32)
+        with ctx._lock:
+            _native.check(_native.lib().m3_search_advance(self._h, _native.ptr(act), _native.ptr(boards), _native.ptr(rew),
+                                                          _native.ptr(na), _native.ptr(legal)))
+        states = []
+        for g in range(n):
+            st = BoardV2(int(na[g]), self._cfgs[g], boards[g].astype(np.int64).reshape(ctx.rows, ctx.columns))
+            st._reward = int(rew[g])
+            st._actions = _native.bits_to_actions(legal[g], ctx.A)
+            states.append(st)
+        self._states = states
+        return self.states()
+
+    def states(self) -> List[BoardV2]:
+        """The current roots."""
+        return [s.clone() for s in self._states]
+
+    # ---- MCTS.__call__ ----------------------------------------------------------------
+    def __call__(self):
+        """``simulations`` rounds for every game, then re-root at the best action, as ``MCTS.__call__``.
+        Returns [(action, value, policies)] per game; policies = child visits / root visits in
+        expansion order. ValueError where ``rollouts()`` raises (a state without a legal action),
+        RuntimeError where a step or a rollout stopped at a shuffle or cascade cap."""
+        if any(s.is_terminal for s in self._states):
+            raise ValueError("search of a terminal state (the reference's MCTS.__call__ raises in its last lines)")
+        seeds = np.empty((self.simulations, self.n), np.uint32)
+        for g, rng in enumerate(self._rngs):  # game by game: each game's seeds in order from its own generator
+            seeds[:, g] = [rng.randint(0, SEED_BOUND) for _ in range(self.simulations)]
+        self.run(seeds)
+        res = self.result(children=False)
+        fl = res["flags"]
+        if (fl & _native.FLAG_NO_LEGAL).any():
+            raise ValueError("a search reached a board with no legal action (np.random.choice of an empty list)")
+        if (fl & _CAPS).any():
+            raise RuntimeError("a step or a rollout of the search stopped at a shuffle or cascade cap "
+                               "(M3_FLAG_SHUFFLE_CAP / M3_FLAG_CASCADE_CAP): the reference would not return")
+        out = []
+        for g in range(self.n):
+            k, rv = int(res["n_children"][g]), int(res["root_visits"][g])
+            out.append((int(res["best_action"][g]), int(res["value"][g]),
+                        [int(v) / rv for v in res["child_visits"][g][:k]]))
+        self.advance(None)
+        return out

@@ -41,7 +41,8 @@ extern "C" {
 #define M3_ERR_RCCL (-4)        /* RCCL error */
 #define M3_ERR_NO_DEVICE (-5)   /* no usable GPU */
 #define M3_ERR_STATE (-6)       /* call out of order (e.g. step before reset) */
-#define M3_ERR_CAP (-7)         /* a safety cap stopped a reset the reference would keep running (see flags) */
+#define M3_ERR_CAP (-7)         /* a safety cap stopped a reset the reference would keep running (see flags);
+                                   m3_search_run: the simulations do not fit the trees' node_capacity */
 
 /* Per-board flags (uint32 out_flags). */
 #define M3_FLAG_TERMINAL 0x01u    /* n_actions < 1: board returned unchanged (boardv2.py:44-45) */
@@ -54,6 +55,7 @@ extern "C" {
 
 typedef struct m3_ctx m3_ctx;
 typedef struct m3_env m3_env;
+typedef struct m3_search m3_search;
 
 int m3_abi_version(void);
 const char *m3_last_error(void);
@@ -147,6 +149,67 @@ int m3_lookahead(m3_ctx *ctx, int64_t n, const int8_t *boards, const uint32_t *s
 int m3_lookahead_device(m3_ctx *ctx, int64_t n, const int8_t *boards, const uint32_t *seeds,
                         const int32_t *n_actions, int32_t *out_best_action, int32_t *out_best_reward,
                         int32_t *out_values, uint32_t *out_last_draws, uint32_t *out_flags);
+
+/* ---- device-resident MCTS trees (mctslib/abc/mcts.py:33-128, standard/mcts.py) ---------- */
+/* n_games UCB1 search trees in device memory, searched in lockstep: one simulation round of every
+ * game is a fixed sequence of launches on the context stream -- selection, the expansion's
+ * apply_action, the attach, the rollout, the backup -- with no host round trip inside a search.
+ * The search is the reference's, node for node: expansion pops the HIGHEST untried action
+ * (untried_actions = list(legal), then pop(): abc/mcts.py:45,60), children keep their expansion
+ * order, every maximum is the first one in that order, and UCB1 is evaluated bit for bit as CPython
+ * evaluates it (doubles, every operation rounded on its own, log from a table filled by the host's
+ * libm: csrc/m3_search_core.hpp). leaf_rollouts > 1 and deterministic=True (match3tile/mcts.py) are
+ * not offered here.
+ *
+ * Memory: every game owns node_capacity node slots of 16 + 32 + 4 * ceil(A/32) + rows*columns bytes
+ * (9x9x6: 149, 16x16x8: 368), never compacted: re-rooting keeps the slots of the dropped siblings.
+ * A search of `simulations` rounds takes at most one slot per game and round;
+ * 2 + moves * simulations slots hold a whole game of `moves` searches.
+ *
+ * A game freezes -- no expansion, no backup for the rest of its life, its flag word set -- where the
+ * reference raises or never returns: a non-terminal node without a legal action (M3_FLAG_NO_LEGAL:
+ * max() of no children, abc/mcts.py:96) and M3_FLAG_SHUFFLE_CAP / M3_FLAG_CASCADE_CAP of a step or a
+ * rollout. The other games go on. */
+int m3_search_create(m3_ctx *ctx, int64_t n_games, int32_t node_capacity, m3_search **out);
+int m3_search_destroy(m3_search *s);
+/* out[v - 1] = log(v) for v = 1..n: the table UCB1's log(parent.visits) is read from, std::log of
+ * the host's libm, which CPython's math.log calls too (standard/mcts.py:36). Host only, needs no GPU. */
+int m3_search_log_table(int32_t n, double *out);
+/* MCTS.__init__ (abc/mcts.py:78-82) for every game: the root node of state (boards[i], cfg.seed =
+ * seeds[i], n_actions[i], reward = rewards[i]) and the constructor's one expansion, without a
+ * rollout. Drops the trees the object held. Host buffers; blocks until done. */
+int m3_search_set_roots(m3_search *s, const int8_t *boards, const uint32_t *seeds, const int32_t *n_actions,
+                        const int32_t *rewards);
+/* `simulations` rounds of MCTS.__call__'s loop (abc/mcts.py:91-109) for every game. rollout_seeds:
+ * host uint32 [simulations][n_games], round-major: the random.randint(0, 2**31 - 1) that
+ * MCTS.rollout draws once per simulation, terminal leaf or not (standard/mcts.py:15), so the caller
+ * pre-draws `simulations` seeds per game from that game's generator, in order. Returns once the seeds
+ * are on their way and the rounds are enqueued; it does not wait for the kernels. M3_ERR_STATE before
+ * m3_search_set_roots. M3_ERR_CAP, with nothing enqueued and the trees untouched, unless
+ * used + simulations + 1 <= node_capacity, used = 1 + the simulations run since m3_search_set_roots. */
+int m3_search_run(m3_search *s, int32_t simulations, const uint32_t *rollout_seeds);
+/* What MCTS.__call__ returns (abc/mcts.py:113-120), without re-rooting: best_action = the action of
+ * the FIRST most-visited root child in expansion order (-1 without a child), value = the reward of
+ * the state where best_child(0) stops descending, root_visits, and the root's n_children children
+ * in expansion order: child_action / child_visits / child_reward [n][A] (the policies are
+ * child_visits / root_visits). flags: the game's M3_FLAG_* word, non-zero = frozen. Every out is
+ * nullable. Host buffers; blocks until the runs before it are done. */
+int m3_search_result(m3_search *s, int32_t *best_action, int32_t *value, int32_t *root_visits, int32_t *n_children,
+                     int32_t *child_action, int32_t *child_visits, int64_t *child_reward, uint32_t *flags);
+/* Re-root every game at the child its action leads to (abc/mcts.py:123-124); actions = NULL: at the
+ * best_action of the last m3_search_result. The subtree keeps its visit counts and reward sums; the
+ * new root has no parent. out_*: the new roots as states (board, reward, n_actions, legal bitset),
+ * each nullable. M3_ERR_INVALID if an action has no expanded child (those games keep their root). */
+int m3_search_advance(m3_search *s, const int32_t *actions, int8_t *out_boards, int32_t *out_rewards,
+                      int32_t *out_n_actions, uint32_t *out_legal_bits);
+/* Since m3_search_set_roots: out[0] node slots used (the maximum over the games, as of the last
+ * m3_search_result), out[1] rounds run, out[2] / out[3] expansions / rollouts recomputed by the
+ * exact pass of the apply / rollout kernels. Blocks. */
+int m3_search_stats(m3_search *s, uint64_t out[4]);
+/* Test hook: Node.ucb1 (standard/mcts.py:33-37) on the device for n independent (reward_sum, visits,
+ * parent_visits >= 1, c) tuples, as the selection kernel evaluates it. Host buffers; blocks. */
+int m3_search_ucb1(m3_ctx *ctx, int64_t n, const int64_t *reward_sum, const int32_t *visits,
+                   const int32_t *parent_visits, const double *c, double *out);
 
 /* ---- device-resident batched env: n x Match3Env (env.py:8-65) ----------- */
 
