@@ -1016,10 +1016,12 @@ M3_HD typename CF::Bd gravity(typename CF::Bd* P, const typename CF::Dim& dm = t
     return gravity_decomp<CF>(P, dm);
 }
 
-// refill of the top-aligned empty cells em
+// refill of the top-aligned empty cells em, one tile placed per accepted draw: every shape but the
+// specialised small one (refill below), that shape's refills of more than 32 tiles, and the
+// reference of tests/refill_host
 template <class CF, class RNG>
-M3_HD void refill(typename CF::Bd* P, const typename CF::Bd& em, RNG& rng,
-                  const typename CF::Dim& dm = typename CF::Dim{}) {
+M3_HD void refill_loop(typename CF::Bd* P, const typename CF::Bd& em, RNG& rng,
+                       const typename CF::Dim& dm = typename CF::Dim{}) {
     using Bd = typename CF::Bd;
     constexpr int C = CF::C, R = CF::R;
     if (!em.any()) return;
@@ -1051,6 +1053,140 @@ M3_HD void refill(typename CF::Bd* P, const typename CF::Bd& em, RNG& rng,
             c = __builtin_ctz(tops);
             r = 0;
         }
+    }
+}
+
+// (src >> off) & low_bits(n) for n <= 31, off taken mod 32 (v_bfe_u32)
+M3_HD uint32_t ubfe(uint32_t src, uint32_t off, uint32_t n) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return __builtin_amdgcn_ubfe(src, off, n);
+#else
+    return (src >> (off & 31u)) & ((1u << (n & 31u)) - 1u);
+#endif
+}
+// a * b for a, b < 2^24 (v_mul_u32_u24: full rate, v_mul_lo_u32 is not)
+M3_HD uint32_t umul24(uint32_t a, uint32_t b) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return __umul24(a, b);
+#else
+    return a * b;
+#endif
+}
+
+template <class RNG>
+struct IsChainMT : std::false_type {};
+template <uint32_t LIMIT>
+struct IsChainMT<ChainMTT<LIMIT>> : std::true_type {};
+
+// Placement of a refill's tile stream (refill below): S[p] bit i = bit p of the i-th accepted tile,
+// tiles in the reference's order -- column by column, top down -- so cell (r, c) of the top-aligned
+// empty set em takes tile off_c + r, off_c = the holes in the columns left of c. At most 32 tiles.
+// No loop over tiles and no lane-divergent branch. Per column: its offset and height from
+// population counts. Per column and plane: one bit-field extract of the column's run (9 bits, row
+// 0 first) and two 24-bit multiplies that lay it out at stride 9 -- x * 0x010101 puts copy j of x
+// at bit 8j, so bit 9r + 3g of the product is bit r + 3g of x: rows 0..2 and 3..5 come out of one
+// product of the run's low six bits (no carries: copies of six bits do not overlap), rows 6..8 out
+// of a second one. The column's place in the row is in the multiplier. Three accumulators per
+// plane (rows 0..2, 3..5, 6..8, each 27 bits), put at bits 0 / 27 / 54 of the plane at the end.
+// (Columns outside, planes inside, em kept from the caller: the forms that walk plane by plane or
+// rebuild em from the planes put k_env_step or k_rollout over their spill counts)
+template <class CF>
+M3_HD void refill_place(typename CF::Bd* P, const typename CF::Bd& em, const uint32_t* S) {
+    using G = typename CF::G;
+    constexpr int C = CF::C, R = CF::R, W = CF::W, NB = CF::BITS;
+    static_assert(R == 9 && C == 9 && W == 3, "the row groups below are laid out for 9 x 9");
+    constexpr uint32_t K = 0x010101u, M = 0x040201u;
+    const uint32_t need = (uint32_t)em.popc();
+    uint32_t g0[NB], g1[NB], g2[NB];
+#pragma unroll
+    for (int p = 0; p < NB; ++p) g0[p] = g1[p] = g2[p] = 0u;
+    uint32_t off = 0u;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const uint32_t nxt = c + 1 < C ? (uint32_t)(em & G::col_le(c)).popc() : need;
+        const uint32_t h = nxt - off;  // 0..9
+#pragma unroll
+        for (int p = 0; p < NB; ++p) {
+            const uint32_t x = ubfe(S[p], off, h);  // (off = 32 only with h = 0)
+            const uint32_t lo = x & 0x3Fu, hi = (x >> 6) & 7u;
+            const uint32_t m = c < 8 ? umul24(lo, K << c) : umul24(lo << c, K);  // (K << 8 is 25 bits)
+            const uint32_t n = c < 8 ? umul24(hi, K << c) : umul24(hi << c, K);
+            g0[p] |= m & (M << c);
+            g1[p] |= m & (M << (c + 3));  // (three bits up from its rows' places)
+            g2[p] |= n & (M << c);
+        }
+        off = nxt;
+    }
+#pragma unroll
+    for (int p = 0; p < NB; ++p) {
+        P[p].w[0] |= g0[p] | (g1[p] << 24);
+        P[p].w[1] |= (g1[p] >> 8) | (g2[p] << 22);
+        P[p].w[2] |= g2[p] >> 10;
+    }
+}
+
+// refill of the top-aligned empty cells em.
+//
+// The specialised small shape (9x9x6) on a chain generator takes it in two parts. (1) Generation:
+// one raw draw per loop trip as in refill_loop, but the loop carries only the chain (a_lo, a_hi, k),
+// the tiles still to come, the next tile's bit and the accepted tiles as a compact stream of one
+// word per tile bit-plane; it has one exit, a rejected draw changes nothing but the chain (selects,
+// no second back edge), and the board planes are not touched in it. It stops with the last accepted
+// tile, so the generator's position is refill_loop's. Only the one-level part of the chain (draws
+// < 227) is in the loop; a lane that crosses draw 227 finishes in a second loop on the generator's
+// own next32() (which also raises the overflow; the planes of an overflowed step do not count, the
+// step is recomputed). (2) Placement, once: refill_place. A refill of more than 32 tiles does not
+// fit the stream words: the wave takes refill_loop, whole, behind a wave-uniform test (1 refill in
+// 10^5 of seeded play, tests/test_refill_cpu.py).
+// Every other shape and generator: refill_loop.
+template <class CF, class RNG>
+M3_HD void refill(typename CF::Bd* P, const typename CF::Bd& em, RNG& rng,
+                  const typename CF::Dim& dm = typename CF::Dim{}) {
+    if constexpr (!CF::DYN && CF::N <= 128 && IsChainMT<RNG>::value) {
+        const uint32_t need = (uint32_t)em.popc();
+#if defined(M3_HOST_REFILL_HOOK) && !defined(__HIP_DEVICE_COMPILE__)
+        M3_HOST_REFILL_HOOK(need);  // (the test harness counts the refill sizes; the library never defines it)
+#endif
+        if (wave_any(need > 32u)) {
+            refill_loop<CF>(P, em, rng, dm);
+            return;
+        }
+        constexpr uint32_t tmask = CF::TILE_MASK, trng = CF::TILE_RNG;
+        uint32_t S[CF::BITS];
+#pragma unroll
+        for (int p = 0; p < CF::BITS; ++p) S[p] = 0u;
+        uint32_t left = need, bit = 1u;  // bit = 1 << (tiles so far); 0 after the 32nd, when left is 0 too
+        {
+            uint32_t a_lo = rng.a_lo, a_hi = rng.a_hi, k = rng.k;
+            while (left != 0u && k < 227u) {
+                const uint32_t lo1 = mt_init_next(a_lo, k + 1u);
+                const uint32_t v = mt_temper(a_hi ^ mt_twist(a_lo, lo1)) & tmask;
+                a_hi = mt_init_next(a_hi, k + 398u);
+                a_lo = lo1;
+                k += 1u;
+                const uint32_t acc = v <= trng ? 1u : 0u;
+                const uint32_t sel = acc ? bit : 0u;
+#pragma unroll
+                for (int p = 0; p < CF::BITS; ++p) S[p] |= (0u - (((v + 1u) >> p) & 1u)) & sel;  // randint(1, T+1)
+                bit <<= acc;
+                left -= acc;
+            }
+            rng.a_lo = a_lo;
+            rng.a_hi = a_hi;
+            rng.k = k;
+        }
+        while (left != 0u) {  // rare: draw 227 and later
+            const uint32_t v = rng.next32() & tmask;
+            if (rng.overflow) break;
+            if (v > trng) continue;
+#pragma unroll
+            for (int p = 0; p < CF::BITS; ++p) S[p] |= (0u - (((v + 1u) >> p) & 1u)) & bit;
+            bit <<= 1;
+            left -= 1u;
+        }
+        refill_place<CF>(P, em, S);
+    } else {
+        refill_loop<CF>(P, em, rng, dm);
     }
 }
 
