@@ -552,14 +552,6 @@ int m3_lookahead(m3_ctx* c, int64_t n, const int8_t* boards, const uint32_t* see
 
 namespace {
 
-// records of the rollout spill pool (a lane keeps one spill record for its whole rollout): one per
-// 8 rollouts (at least 4096), within 256 MB (a lane that finds the pool empty is replayed exactly
-// by k_rollout_fix)
-int64_t rollout_spill_cap(int64_t n, size_t words) {
-    const int64_t budget = (int64_t)((256ull << 20) / (words * 4ull));
-    return std::max<int64_t>(1, std::min(std::max<int64_t>(4096, n / 8), budget));
-}
-
 size_t rollout_spill_words(int shape) {
     return (size_t)with_shape(shape, [&](auto cf) {
         using CF = decltype(cf);

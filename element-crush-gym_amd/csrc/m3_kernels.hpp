@@ -5,6 +5,11 @@
 // instantiates that configuration's launchers -- and with them its kernels --
 // so the configurations compile in parallel translation units. A single-TU
 // build (m3_api.hip without -DM3_SPLIT_TU) instantiates everything implicitly.
+//
+// The geometry and tunables (KS), the record sizes and what the stateless apply and the rollouts do
+// per board (apply_and_emit, rollout_one) are in m3_batch_core.hpp, which the host harnesses under
+// tests/ compile too. Here: the LDS stores and staging, the env step (env_step_one, the wave-level
+// epilogue env_fin_*), the reset kernels, the kernels themselves and their launchers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -18,9 +23,11 @@
 #include <vector>
 
 #include "../../include/m3.h"
-#include "m3_rules.hpp"
+#include "m3_batch_core.hpp"
 
 using namespace m3;
+using m3k::ApplyArgs;
+using m3k::RolloutArgs;
 
 // defined in m3_api.hip: sets the thread-local m3_last_error() message, returns code
 int set_err(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
@@ -47,32 +54,8 @@ namespace {
         if (!(cond)) return set_err(M3_ERR_INVALID, "%s", (msg)); \
     } while (0)
 
-constexpr int BLOCK = 256;
-constexpr int FIX_BLOCK = 64;
-constexpr int FIX_GRID = 16;       // step fixup almost never has work: few blocks schedule fast
-constexpr int INIT_FIX_BLOCK = 64;
-constexpr int INIT_BLOCK = 64;
-// active lanes of the one-board-per-lane fix / reset kernels (KS::BPW: one for the 32 x 32 frame)
-template <class CF>
-constexpr uint32_t lanes_for() { return CF::W > 8 ? 1u : 64u; }
-// 9x9: k_init redoes its few > 624-draw resets in-wave (wave_reset); 16x16
-// resets go straight to k_init_fix_lane (most need >= 624 draws)
-template <class CF>
-constexpr bool INIT_INLINE_FIX = CF::N <= 128;
 constexpr int MAX_SHARDS = 8;  // env board shards (one HIP stream each)
-// The M3_* macros of the device sources are of three kinds only: numeric tunings that `make variant
-// XFLAGS=-D...` varies (the #ifndef-guarded numbers, from here on and M3_TW9 / M3_LEGAL_SLICED_W in
-// m3_rules.hpp), M3_FAST_MATCH (m3_rules.hpp: the host test compares both sides), and build structure
-// / diagnostic builds (M3_SPLIT_TU, M3_INST, M3_PART, M3_HEADLINE_ONLY, M3_NO_WIDE_FRAME;
-// M3_PHASE_PROF, M3_TEST_NO_GATHER_WAIT, M3_DEBUG_NO_PREFETCH). On/off switches of variants that were
-// measured and rejected are not kept: DESIGN.md has their numbers, git history their code.
-// k_init's lockstep draw budget when it may defer (env prefetch): 9x9x6 resets
-// past 454 draws (~4 %: the third chain level and the second block) go to
-// k_init_coop, so a wave no longer runs to its slowest lane's ~600 draws
-#ifndef M3_RESET_KCAP
-#define M3_RESET_KCAP 454
-#endif
-constexpr uint32_t RESET_KCAP = M3_RESET_KCAP;
+// (the M3_* tuning macros: see m3_batch_core.hpp)
 // The prefetch reset launches are sized for n / PF_DIV queued resets of the shard (grid-strided beyond
 // that; blocks past the queue's length exit at once). Round 6: every board's episode ends on the same
 // step (the bench's 20-move episodes all start together), so one step in 20 queues the whole shard;
@@ -88,78 +71,6 @@ constexpr uint32_t RESET_KCAP = M3_RESET_KCAP;
 #ifndef M3_COOP_GMAX  // most blocks of a prefetch k_init_coop launch (one deferred reset per wave at a time)
 #define M3_COOP_GMAX 4096
 #endif
-// A reset stops after this many rounds of BoardV2.__init__'s redraw loop (boardv2.py:23-27) and
-// flags M3_FLAG_RESET_CAP: only two-colour boards get near it (a 16x16x2 reset can need more than
-// 10,000 rounds; the reference keeps going), and a GPU lane must end.
-constexpr uint32_t RESET_ROUND_CAP = 1u << 14;
-
-// Per-shape step-kernel geometry: boards (lanes) per workgroup and the
-// match-group table capacity, sized so staging + table fit the 160 KB LDS.
-// One wave per workgroup: the boards of a wave are staged through its own LDS
-// slice, so a wave that finishes early never waits at a barrier for the
-// workgroup's slowest wave (cascade depth varies a lot between boards) and its
-// slot is refilled at once.
-template <class CF>
-struct KS {
-    static constexpr int B = 64;
-    static_assert(B == 64, "one-wave workgroups: lds_sync() orders a single wave's LDS accesses");
-    // match groups in LDS per lane (more spill to a global pool): 9x9 6 (9 KB per wave, +0.8 %,
-    // gpurun_out/r05aj), 16x16 4 (past the staging area a larger table costs occupancy)
-    static constexpr int GCAP = CF::N <= 128 ? 6 : 4;
-    // boards per wave: 64 (one per lane), but ONE for the 32 x 32 frame. Those kernels carry
-    // ~2,500 SGPR spills through VGPR lanes, and with several lanes active some boards came out
-    // wrong only in company (32x32x8 steps: 92 of 689; each exact alone) -- the lane interference
-    // DESIGN.md §4 describes for the 16 x 16 frame. One active lane per wave has no divergence.
-    static constexpr int BPW = CF::W > 8 ? 1 : B;
-#ifndef M3_STEP_WPS
-#define M3_STEP_WPS 4
-#endif
-    // k_env_step waves per SIMD the register allocation is bounded for (16x16:
-    // 2, with 708 B of spill, +7 % over 1 once resets stopped binding)
-#ifndef M3_STEP_WPS16
-#define M3_STEP_WPS16 2
-#endif
-    // frame shapes (run-time board shape, FCfg): 1 wave/SIMD. Their uniform shape masks take
-    // ~100 SGPRs and spill into VGPR lanes; at 2 waves/SIMD those VGPRs spilled to scratch in
-    // turn and divergent lanes of a wave corrupted each other's results (rollouts at 10x8x9,
-    // tools/dbg); with 512 registers per lane nothing reaches scratch.
-#ifndef M3_STEP_WPS_FRAME
-#define M3_STEP_WPS_FRAME 1
-#endif
-    static constexpr int STEP_WPS = CF::DYN ? M3_STEP_WPS_FRAME : (CF::N > 128 ? M3_STEP_WPS16 : M3_STEP_WPS);
-    // k_env_cont: bounded like the step kernel it runs beside (a 2-waves/SIMD
-    // build without spills measured 4 % slower overall: its waves take register
-    // file the other shard's step waves need)
-#ifndef M3_CONT_WPS
-#define M3_CONT_WPS M3_STEP_WPS
-#endif
-    static constexpr int CONT_WPS = CF::N > 128 ? 1 : M3_CONT_WPS;
-    // spill pool records per shard (32 x 32 frame: a record is 86 KB; fewer, the rest recompute)
-    static constexpr uint32_t SPILL_RECORDS = CF::W > 8 ? 256 : 4096;
-    // The env step's RNG is the register-only MT19937 chain from the board's
-    // (seed, mt[397]) -- 4 B of per-board state (a per-board stream cache of
-    // the first raw outputs, built by the reset, measured equal at 9x9 and 2x
-    // slower at 16x16; removed in round 3).
-    // 16x16: one chain level (draws < 227; a step needing more -- a near-full
-    // board refill -- goes to k_env_fix), five fewer VGPRs live through the
-    // cascade, +2.5 %. 9x9: the full three-level chain; the one-level build
-    // came out 16 % slower (A/B gpurun_out/ab3), the register allocation of
-    // the 3-waves/SIMD bound shifts with it.
-    using Chain = std::conditional_t<(CF::N > 128), ChainMT1, ChainMT>;
-    using Rng = Chain;
-#ifndef M3_CASCADE_LIMIT
-#define M3_CASCADE_LIMIT 2
-#endif
-    // k_env_step runs at most this many cascade iterations per step (-1: no
-    // bound); longer steps are finished by k_env_cont (see there)
-    // (16x16: off -- the continuation launch cost more than it saved:
-    // 0.364 vs 0.337 G env-steps/s at 1 wave/SIMD, 0.391 vs 0.384 at 2)
-#ifndef M3_CASCADE_LIMIT16
-#define M3_CASCADE_LIMIT16 -1
-#endif
-    static constexpr int CASCADE_LIMIT = CF::N > 128 ? M3_CASCADE_LIMIT16 : M3_CASCADE_LIMIT;
-};
-
 // LDS pointers carry their address space, so table accesses compile to ds_*
 // instructions: a generic pointer that may point at either the LDS table or
 // the global spill pool made the compiler emit flat loads, and every wait on a
@@ -215,7 +126,7 @@ struct LdsStore {
     static constexpr int W = CF::W;
     static constexpr int BLOCK = LANES;
     static constexpr int WORDS = LCAP * 2 * W * BLOCK;
-    static constexpr int SPILL_WORDS = (CF::MAXG - LCAP) * 2 * W;  // per pool record
+    static constexpr int SPILL_WORDS = SPILL_REC_WORDS<CF, LCAP>;  // per pool record
     lds_u32* tab;         // already offset by threadIdx.x
     uint32_t* spill;      // nullable: pool of records
     uint32_t* pool_next;  // pool allocation counter
@@ -477,14 +388,6 @@ __device__ __forceinline__ void bytes_to_planes(const int8_t* src, typename CF::
     planes_from_words<CF>(cw, P);
 }
 
-template <class CF>
-__device__ __forceinline__ void store_legal(uint32_t* out, const uint32_t* act,
-                                            const typename CF::Dim& dm = typename CF::Dim{}) {
-#pragma unroll
-    for (int i = 0; i < CF::AW; ++i)
-        if (i < dm.aw()) out[i] = act[i];
-}
-
 // words of one board's cells as packed little-endian words (env episode slots)
 template <class CF>
 __device__ __forceinline__ int cell_words(const typename CF::Dim& dm) {
@@ -495,57 +398,6 @@ __device__ __forceinline__ int cell_words(const typename CF::Dim& dm) {
 // stateless kernels (BoardV2 facade): m3_apply_actions / m3_init_boards /
 // m3_legal_actions
 // ---------------------------------------------------------------------------
-}  // namespace
-// launcher signatures name this struct: it needs linkage (m3_inst.hip instantiates them)
-namespace m3k {
-struct ApplyArgs {
-    Shape shape;  // the board (frame kernels; the specialised ones ignore it)
-    int64_t n;
-    const int8_t* boards;
-    const uint32_t* seeds;
-    const int32_t* n_actions;
-    const int32_t* actions;
-    int8_t* out_boards;
-    int32_t* reward;
-    uint32_t* draws;
-    uint32_t* flags;
-    uint32_t* legal;       // nullable
-    int32_t* next_action;  // nullable
-    uint32_t* ovf_count;
-    uint32_t* ovf_list;
-    uint32_t* bad_cells;   // nullable: set to 1 if a cell value lies outside [0, 127]
-    int clear_ovf;         // k_apply_fix (one block) zeroes *ovf_count when done (zero-copy calls)
-};
-}  // namespace m3k
-using m3k::ApplyArgs;
-namespace {
-
-// one full apply_action + outputs for board b; returns false on RNG overflow
-template <class CF, class RNG, class Store>
-__device__ __forceinline__ bool apply_and_emit(typename CF::Bd* P, const ApplyArgs& a, int64_t b, RNG& rng,
-                                               Store& st, const typename CF::Dim& dm) {
-    typename CF::Bd HL, VL;
-    uint32_t f;
-    const int r = apply_action<CF>(P, a.n_actions[b], a.actions[b], rng, f, HL, VL, st, dm);
-    if (f & FLAG_RECOMPUTE) return false;
-    const bool stepped = !(f & (FLAG_TERMINAL | FLAG_BAD_ACTION));
-    a.reward[b] = r;
-    a.draws[b] = stepped ? rng.draws() : 0u;
-    uint32_t act[CF::AW];
-    action_bits<CF>(HL, VL, act, dm);
-    int na = -1;
-    if (stepped) {
-        na = random_action<CF>(act, rng);
-        if (rng.overflow) return false;
-        if (na < 0) f |= FLAG_NO_LEGAL;
-    }
-    mark<PH_NEXT>(st);
-    a.flags[b] = f;
-    if (a.next_action) a.next_action[b] = na;
-    if (a.legal) store_legal<CF>(a.legal + b * dm.aw(), act, dm);
-    return true;
-}
-
 template <class CF>
 __global__ void __launch_bounds__(KS<CF>::B) k_apply(ApplyArgs a) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[KS<CF>::B * CF::N + 16];
@@ -598,13 +450,6 @@ __global__ void __launch_bounds__(FIX_BLOCK) k_apply_fix(ApplyArgs a) {
     }
 }
 
-// M3_NSLOT: episode slots per board (A/B knob; at most 5: the counter blocks below). Round 6 A/B
-// of 5 slots -- one more step of slack for the synchronised end-of-episode reset bursts: equal speed.
-#ifndef M3_NSLOT
-#define M3_NSLOT 4
-#endif
-constexpr int NSLOT = M3_NSLOT;     // episode slots per board (see EnvArgs)
-static_assert(NSLOT >= 2 && NSLOT <= 255, "slot index is a byte");
 constexpr int PF_LAG = NSLOT - 1;   // steps between a prefetch and its first use
 // Per-shard counter blocks (8 words each), by step % CBLOCKS. Step t's block is read last by its
 // prefetch chain, which step t + PF_LAG waits for; so when step t + PF_LAG's k_env_fix runs, the
@@ -1649,18 +1494,10 @@ __device__ __forceinline__ bool env_finish(typename CF::Bd* P, const EnvArgs& a,
     return true;
 }
 
-enum : int { ENV_STEP_DONE = 0, ENV_STEP_RECOMPUTE = 1, ENV_STEP_PAUSED = 2 };
-
-// internal: a continuation record of a settled board with no legal move (the
-// row shuffle comes next), as opposed to one paused before a cascade iteration
-constexpr uint32_t FLAG_CONT_DEAD = 0x80u;
-
-// One Match3Env.step of board b. With DEFER (k_env_step), the cascade stops
-// after `limit` inner iterations and at a dead board (the shuffle path is left
-// out of the kernel): the step returns ENV_STEP_PAUSED with its state in P,
-// rng, r, f (f & FLAG_CONT_DEAD: dead) and has written nothing yet; k_env_cont_grid
-// finishes it. Without DEFER the whole step runs here.
-template <class CF, bool DEFER, class RNG, class Store>
+// One Match3Env.step of board b, whole: the cascade runs to its end here (k_env_fix, and k_env_step
+// where KS::CASCADE_LIMIT is off). ENV_STEP_RECOMPUTE: the chain or the group table ran out and
+// nothing has been written.
+template <class CF, class RNG, class Store>
 __device__ __forceinline__ int env_step_one(typename CF::Bd* P, const EnvArgs& a, int64_t b, RNG& rng, Store& st,
                                             int limit, int& r, uint32_t& f, const typename CF::Dim& dm,
                                             uint8_t* row = nullptr, FinOpts o = FinOpts{}) {
@@ -1670,7 +1507,7 @@ __device__ __forceinline__ int env_step_one(typename CF::Bd* P, const EnvArgs& a
     const int sc0 = a.score[b];
     typename CF::Bd HL, VL;
     if (apply_begin<CF>(P, a.num_moves - mv, act_in, rng, f, HL, VL, st, r, dm)) {
-        const int c = apply_cascade_ex<CF, DEFER ? CASX_STOP_DEAD : 0>(P, rng, f, HL, VL, st, r, limit, false, dm);
+        const int c = apply_cascade_ex<CF, 0>(P, rng, f, HL, VL, st, r, limit, false, dm);
         if (!(f & FLAG_RECOMPUTE)) {
             if (c == CAS_PAUSED) return ENV_STEP_PAUSED;
             if (c == CAS_DEAD) {
@@ -1684,17 +1521,7 @@ __device__ __forceinline__ int env_step_one(typename CF::Bd* P, const EnvArgs& a
                                                                                       : ENV_STEP_RECOMPUTE;
 }
 
-// Continuation records of paused steps (KS::CASCADE_LIMIT): word 0 the
-// shard-local board index, words 1.. the Cont state, padded to CONT_REC words
-// (9x9x6: 32 words, 128 B) so a lane writes and reads its record with 16-byte
-// accesses -- 8 instructions each way instead of one per word (round 5 wrote them
-// SoA, word w of record q at cont[w * n + q]: 31 stores per wave). Record q at
-// cont[q * CONT_REC]; the step's counter block [CNT_CONT] counts them.
-template <class CF>
-using EnvCont = Cont<CF, typename KS<CF>::Rng>;
-template <class CF>
-constexpr int CONT_REC = (1 + EnvCont<CF>::WORDS + 3) & ~3;
-
+// continuation records (EnvCont, CONT_REC: m3_batch_core.hpp) to and from memory, 16 bytes at a time
 template <class CF>
 __device__ __forceinline__ void cont_store(uint32_t* rec, uint32_t b, const typename CF::Bd* P,
                                            const typename KS<CF>::Rng& rng, int r, uint32_t f) {
@@ -1778,8 +1605,8 @@ __global__ void __launch_bounds__(KS<CF>::B, KS<CF>::STEP_WPS) k_env_step(EnvArg
         // a finished step leaves its board bytes (or the next episode's) in its staging row
         uint8_t* const row = lds + t * (NC + RPAD);
         if constexpr (K::CASCADE_LIMIT >= 0) {  // (a.cont is set)
-            // env_step_one<CF, true> with the epilogue split round one atomic per wave: the
-            // decisions of every lane (paused, or finished and resetting), then the wave's
+            // the front of env_step_one with a bounded cascade, and the epilogue split round one atomic
+            // per wave: the decisions of every lane (paused, or finished and resetting), then the wave's
             // continuation records and prefetch queue entries in one 64-bit atomicAdd, then the
             // stores (see env_finish)
             const int act_in = a.actions ? a.actions[b] : a.next_action[b];
@@ -1851,7 +1678,7 @@ __global__ void __launch_bounds__(KS<CF>::B, KS<CF>::STEP_WPS) k_env_step(EnvArg
                 o.reset = &reset_lane;
                 o.ob = &reset_ob;
             }
-            res = env_step_one<CF, false>(P, a, b, rng, st, -1, r, f, dm, row, o);
+            res = env_step_one<CF>(P, a, b, rng, st, -1, r, f, dm, row, o);
             if (res == ENV_STEP_RECOMPUTE) {  // (its row is rewritten by k_env_fix)
                 const uint32_t slot = atomicAdd(&a.counters[CNT_OVF], 1u);
                 a.ovf_list[slot] = (uint32_t)b;
@@ -1934,94 +1761,21 @@ __global__ void __launch_bounds__(FIX_BLOCK, 1) k_env_fix(EnvArgs a) {
             // latency on the step's critical path
             ChainMT cm;
             cm.init(a.seeds[b], a.m397[(int64_t)a.slot[b] * a.cstride + b]);
-            res = env_step_one<CF, false>(P, a, b, cm, st, -1, r, f, dm);
+            res = env_step_one<CF>(P, a, b, cm, st, -1, r, f, dm);
             if (res == ENV_STEP_RECOMPUTE) bytes_to_planes<CF>(a.cur + b * dm.cells(), P, dm);
         }
         if (res == ENV_STEP_RECOMPUTE) {  // >= 624 draws
             FullMT mt;  // scratch (see k_apply_fix)
             mt.init(a.seeds[b], 0u);
-            env_step_one<CF, false>(P, a, b, mt, st, -1, r, f, dm);
+            env_step_one<CF>(P, a, b, mt, st, -1, r, f, dm);
         }
         planes_to_bytes<CF>(P, reinterpret_cast<uint8_t*>(a.nxt + b * dm.cells()), dm);
     }
 }
 
 // ---------------------------------------------------------------------------
-// batched MCTS rollouts (mctslib/standard/mcts.py:14-19)
+// batched MCTS rollouts (rollout_one, m3_batch_core.hpp)
 // ---------------------------------------------------------------------------
-// One rollout per lane: np.random.seed(rseed); while n_actions >= 1:
-// action = choice(legal_actions) from the global stream, state =
-// apply_action(action). The first choice reads the stream of rseed; every
-// later one reads the stream apply_action left behind (cfg.seed reseeded at
-// boardv2.py:46, advanced by the step's draws), i.e. the same register chain
-// the step just used. The match-group table is the env's LDS table + spill
-// pool, and a lane keeps its spill record for the whole rollout; a rollout
-// that overflows the chain (>= 624 draws in one step) or the pool is
-// replayed from its first move by k_rollout_fix.
-}  // namespace
-// launcher signatures name this struct: it needs linkage (m3_inst.hip instantiates them)
-namespace m3k {
-struct RolloutArgs {
-    Shape shape;
-    int64_t n;
-    const int8_t* boards;
-    const uint32_t* seeds;     // cfg.seed of each state
-    const int32_t* n_actions;
-    const uint32_t* rseeds;    // rollout seed (random.randint(0, 2**31 - 1) or state.seed)
-    int32_t* gain;             // sum of the step rewards of the rollout
-    int32_t* steps;            // apply_action calls
-    uint32_t* draws;           // global-stream draws since its last seed when the rollout ends
-    uint32_t* flags;           // OR of the steps' M3_FLAG_*
-    int8_t* out_boards;        // nullable: terminal boards
-    uint32_t* counters;        // [0] overflow count, [1] spill records taken, [2] waves with a bad cell
-    uint32_t* ovf_list;
-    uint32_t* spill;
-    uint32_t spill_cap;
-};
-}  // namespace m3k
-using m3k::RolloutArgs;
-namespace {
-
-template <class CF, class RNG, class Store>
-__device__ __forceinline__ bool rollout_one(typename CF::Bd* P, const RolloutArgs& a, int64_t b, RNG& first, RNG& rng,
-                                            Store& st, const typename CF::Dim& dm) {
-    int n = a.n_actions[b];
-    int gain = 0, steps = 0;
-    uint32_t fl = 0u, dr = 0u;
-    if (n >= 1) {                                               // mcts.py:16 while not is_terminal
-        typename CF::Bd HL, VL;
-        legal_masks<CF>(P, special_mask<CF, CF::NP>(P), HL, VL, dm);
-        uint32_t act[CF::AW];
-        action_bits<CF>(HL, VL, act, dm);
-        int x = random_action<CF>(act, first);                  // mcts.py:17, stream of the rollout seed
-        dr = first.draws();
-        for (;;) {
-            if (x < 0) {                                        // np.random.choice([]) raises
-                fl |= FLAG_NO_LEGAL;
-                break;
-            }
-            uint32_t f;
-            const int r = apply_action<CF>(P, n, x, rng, f, HL, VL, st, dm);  // mcts.py:18
-            if (f & FLAG_RECOMPUTE) return false;
-            fl |= f;
-            gain += r;
-            ++steps;
-            --n;
-            dr = rng.draws();
-            if (n < 1) break;
-            action_bits<CF>(HL, VL, act, dm);
-            x = random_action<CF>(act, rng);                    // stream where apply_action left it
-            if (rng.overflow) return false;
-            dr = rng.draws();
-        }
-    }
-    a.gain[b] = gain;
-    a.steps[b] = steps;
-    a.draws[b] = dr;
-    a.flags[b] = fl;
-    return true;
-}
-
 template <class CF>
 __global__ void __launch_bounds__(KS<CF>::B, KS<CF>::STEP_WPS) k_rollout(RolloutArgs a) {
     using K = KS<CF>;

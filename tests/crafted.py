@@ -1,6 +1,6 @@
 """Boards crafted to fill the match-group table (numpy and the oracle only; shape-generic).
 
-The kernels keep the first LCAP match groups of a scan in LDS (KS::GCAP, m3_kernels.hpp: 6 at
+The kernels keep the first LCAP match groups of a scan in LDS (KS::GCAP, m3_batch_core.hpp: 6 at
 9x9x6, 4 at 16x16x8 and in the frames), further groups in a record of a global spill pool, and hand a
 board over to an exact recompute when the pool is full or the register MT19937 chain runs out.
 Seeded play gets there about once in a thousand steps and the fixtures never do, so these boards
@@ -44,9 +44,39 @@ def _kernel_cells(shape):
     return R * C if tuple(shape) in SPECIALISED else (256 if max(R, C) <= 16 else 1024)
 
 
+# The kernels' constants that the tests restate (KS<CF> and its neighbours in m3_batch_core.hpp), as
+# literals: the GPU tests need no host build. test_crafted_cpu holds every one of them to the values
+# compiled into the host harness (hostcore's hc_geometry).
+POOL = 4096          # KS::SPILL_RECORDS per shard and step, and rollout_pool(n) for n <= 32768
+FIX_LANES = 1024     # FIX_GRID x 64: the fix kernels' lanes; more work takes their grid-stride loop
+NSLOT = 4            # episode slots per board: a freed slot takes the episode NSLOT - 1 ahead
+RESET_KCAP_9 = 454   # k_init<CF, false> gives up a prefetched 9x9x6 reset past this many draws
+
+
+def _wide(shape):
+    """the 32 x 32 frame: one board per wave, and a spill record of 86 KB"""
+    return tuple(shape) not in SPECIALISED and max(shape[0], shape[1]) > 16
+
+
+def pool(shape):
+    """KS<CF>::SPILL_RECORDS: spill-pool records per shard and step"""
+    return 256 if _wide(shape) else POOL
+
+
+def fix_lanes(shape):
+    """FIX_GRID x lanes_for<CF>(): boards one turn of a fix kernel's grid-stride loop takes"""
+    return 16 if _wide(shape) else FIX_LANES
+
+
+def rollout_pool(n):
+    """rollout_spill_cap below its 256 MB budget (every shape outside the 32 x 32 frame, where the
+    budget is the smaller): records of the spill pool of a launch of n rollouts"""
+    return max(POOL, n // 8)
+
+
 def lcap(shape):
-    """KS<CF>::GCAP (m3_kernels.hpp): match groups per lane in LDS -- 6 for 9x9x6, 4 for 16x16x8
-    and for every frame shape (pinned to the source by test_crafted_cpu)."""
+    """KS<CF>::GCAP (m3_batch_core.hpp): match groups per lane in LDS -- 6 for 9x9x6, 4 for 16x16x8
+    and for every frame shape (held to the compiled value by test_crafted_cpu)."""
     return 6 if _kernel_cells(shape) <= 128 else 4
 
 

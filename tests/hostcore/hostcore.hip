@@ -1,8 +1,11 @@
-// TEST-ONLY host build of the device rule code (element-crush-gym_amd/csrc/m3_rules.hpp).
-// The same __host__ __device__ functions the HIP kernels run are called here
-// on the CPU so their logic can be differential-tested against the oracle in
-// a GPU-less container. Not part of the product; the product library never
-// contains or calls this file.
+// TEST-ONLY host build of the device rule code (element-crush-gym_amd/csrc/m3_rules.hpp) and of the
+// batched paths' per-board code (m3_batch_core.hpp). The same __host__ __device__ functions the HIP
+// kernels run are called here on the CPU so their logic can be differential-tested against the
+// oracle in a GPU-less container: the stateless step is k_apply's apply_and_emit, a rollout is
+// k_rollout's rollout_one, and the table capacity, chain and record layout of the env step come from
+// KS<CF> / EnvCont<CF> (hc_geometry reports them to the tests). The env kernels' own cascade calls
+// and their wave-level epilogue (m3_kernels.hpp) are restated in step_paused. Not part of the
+// product; the product library never contains or calls this file.
 //
 // Shapes: cfg 0 = Cfg<9,9,6>, cfg 1 = Cfg<16,16,8> (the specialised kernels'
 // configs), cfg 2 = the frame (FCfg: 16 x 16, or 32 x 32 for a side > 16) for
@@ -21,7 +24,7 @@ static inline bool hc_wave_any(bool p) {
     return true;
 }
 #define M3_HOST_WAVE_ANY(p) hc_wave_any(p)
-#include "../../element-crush-gym_amd/csrc/m3_rules.hpp"
+#include "../../element-crush-gym_amd/csrc/m3_batch_core.hpp"
 
 #include <stdlib.h>
 #include <string.h>
@@ -58,126 +61,128 @@ static void store_planes(const typename CF::Bd* P, int8_t* b, const typename CF:
     }
 }
 
-// One apply_action + next random action, the way the kernels do it: fast
-// path first (ChainMT + a group table of capacity CAP), full recompute
-// (FullMT + ArrayStore) when the fast path reports overflow.
-// pause >= 0: the env kernel's bounded cascade -- stop before inner
-// iteration pause + 1, serialize the state through Cont into words, restore
-// it into fresh variables and finish the cascade from there.
-template <class CF, class Store, class Chain = ChainMT>
-static int step_one(typename CF::Bd* P, const int8_t* board, uint32_t seed, int na, int act, Store& st,
-                    uint32_t& f, int32_t& draws, uint32_t* legal, int32_t& next_act, int& recomputed,
-                    const typename CF::Dim& dm, int pause = -1, int* paused = nullptr) {
-    typename CF::Bd HL, VL;
+// The exact pass behind every fast path (k_apply_fix): board i again from its bytes, with the full
+// generator and the full group table.
+template <class CF>
+static void step_exact(typename CF::Bd* P, const m3k::ApplyArgs& a, long i, int& recomputed,
+                       const typename CF::Dim& dm) {
+    recomputed++;
+    FullMT* fm = new FullMT;
+    ArrayStore<CF>* as = new ArrayStore<CF>;
+    load_planes<CF>(a.boards + i * dm.cells(), P, dm);
+    fm->init(a.seeds[i], 0);
+    apply_and_emit<CF>(P, a, i, *fm, *as, dm);
+    delete fm;
+    delete as;
+}
+
+// One apply_action + next random action of board i as k_apply runs it: apply_and_emit on the fast
+// path (Chain + the caller's group table), the exact pass when that gives up.
+template <class CF, class Chain = ChainMT, class Store>
+static void step_one(typename CF::Bd* P, const m3k::ApplyArgs& a, long i, Store& st, int& recomputed,
+                     const typename CF::Dim& dm) {
     Chain rng;
-    rng.init(seed, mt_state397(seed));
+    rng.init(a.seeds[i], mt_state397(a.seeds[i]));
+    if (!apply_and_emit<CF>(P, a, i, rng, st, dm)) step_exact<CF>(P, a, i, recomputed, dm);
+}
+
+// The env kernels' bounded cascade, with KS<CF>'s chain: k_env_step stops before inner iteration
+// pause + 1 or at a dead board (before the row shuffle, marked FLAG_CONT_DEAD) and hands the state
+// over through the EnvCont words; k_env_cont_grid restores it into fresh variables and finishes the
+// cascade, dead boards from the shuffle on. Then the step's draws and the next random action as
+// env_fin_begin takes them; a step past the chain or the table goes to the exact pass.
+// Returns whether the step paused.
+template <class CF, class Store>
+static bool step_paused(typename CF::Bd* P, const m3k::ApplyArgs& a, long i, Store& st, int& recomputed,
+                        const typename CF::Dim& dm, int pause) {
+    typename CF::Bd HL, VL;
+    typename KS<CF>::Rng rng;
+    rng.init(a.seeds[i], mt_state397(a.seeds[i]));
     int r;
-    if (pause < 0) {
-        r = apply_action<CF>(P, na, act, rng, f, HL, VL, st, dm);
-    } else {
-        // as the env kernels run it: k_env_step stops after `pause` iterations or at a
-        // dead board (before the row shuffle) and hands the state over through the
-        // Cont words; k_env_cont finishes the cascade, dead boards from the shuffle on
-        if (apply_begin<CF>(P, na, act, rng, f, HL, VL, st, r, dm)) {
-            const int c = apply_cascade_ex<CF, CASX_STOP_DEAD>(P, rng, f, HL, VL, st, r, pause, false, dm);
-            if ((c == CAS_PAUSED || c == CAS_DEAD) && !(f & FLAG_RECOMPUTE)) {
-                using K = Cont<CF, Chain>;
-                uint32_t rec[K::WORDS];
-                K::save(P, rng, r, f, [&](int i, uint32_t w) { rec[i] = w; });
-                typename CF::Bd Q[CF::NP];
-                Chain g2;
-                int r2;
-                uint32_t f2;
-                K::load(Q, g2, r2, f2, [&](int i) { return rec[i]; });
-                apply_cascade_ex<CF, 0>(Q, g2, f2, HL, VL, st, r2, -1, c == CAS_DEAD, dm);
-                memcpy(P, Q, sizeof(Q));
-                rng = g2;
-                r = r2;
-                f = f2;
-                if (paused) ++*paused;
-            }
+    uint32_t f;
+    bool paused = false;
+    if (apply_begin<CF>(P, a.n_actions[i], a.actions[i], rng, f, HL, VL, st, r, dm)) {
+        const int c = apply_cascade_ex<CF, CASX_STOP_DEAD>(P, rng, f, HL, VL, st, r, pause, false, dm);
+        if ((c == CAS_PAUSED || c == CAS_DEAD) && !(f & FLAG_RECOMPUTE)) {
+            if (c == CAS_DEAD) f |= FLAG_CONT_DEAD;
+            uint32_t rec[EnvCont<CF>::WORDS];
+            EnvCont<CF>::save(P, rng, r, f, [&](int k, uint32_t w) { rec[k] = w; });
+            typename CF::Bd Q[CF::NP];  // (fresh variables: only what the record holds comes back)
+            typename KS<CF>::Rng g2;
+            int r2;
+            uint32_t f2;
+            EnvCont<CF>::load(Q, g2, r2, f2, [&](int k) { return rec[k]; });
+            memcpy(P, Q, sizeof(Q));
+            rng = g2;
+            r = r2;
+            f = f2;
+            const bool dead = (f & FLAG_CONT_DEAD) != 0;
+            f &= ~FLAG_CONT_DEAD;
+            apply_cascade_ex<CF, 0>(P, rng, f, HL, VL, st, r, -1, dead, dm);
+            paused = true;
         }
-        if (f & FLAG_RECOMPUTE) r = 0;
     }
-    uint32_t act_bits[CF::AW];
-    int32_t nx = -1;
-    const int32_t step_draws = (int32_t)rng.draws();  // apply_action's draws, before the next choice
-    if (!(f & FLAG_RECOMPUTE) && !(f & (FLAG_TERMINAL | FLAG_BAD_ACTION))) {
-        action_bits<CF>(HL, VL, act_bits, dm);
-        nx = random_action<CF>(act_bits, rng);  // the next action's draws may pass the chain's reach too
+    if (!(f & FLAG_RECOMPUTE)) {
+        const bool stepped = !(f & (FLAG_TERMINAL | FLAG_BAD_ACTION));
+        a.reward[i] = r;
+        a.flags[i] = f;
+        a.draws[i] = stepped ? rng.draws() : 0u;  // apply_action's draws, before the next choice
+        uint32_t act[CF::AW];
+        action_bits<CF>(HL, VL, act, dm);
+        a.next_action[i] = stepped ? random_action<CF>(act, rng) : -1;  // (may pass the chain's reach too)
         if (rng.overflow) f |= FLAG_RNG_OVERFLOW;
+        if (a.legal) store_legal<CF>(a.legal + i * dm.aw(), act, dm);
     }
-    if (f & FLAG_RECOMPUTE) {
-        recomputed++;
-        FullMT* fm = new FullMT;
-        ArrayStore<CF>* as = new ArrayStore<CF>;
-        load_planes<CF>(board, P, dm);
-        fm->init(seed, 0);
-        r = apply_action<CF>(P, na, act, *fm, f, HL, VL, *as, dm);
-        draws = (f & (FLAG_TERMINAL | FLAG_BAD_ACTION)) ? 0 : (int32_t)fm->k;
-        action_bits<CF>(HL, VL, act_bits, dm);
-        next_act = (f & (FLAG_TERMINAL | FLAG_BAD_ACTION)) ? -1 : random_action<CF>(act_bits, *fm);
-        delete fm;
-        delete as;
-    } else {
-        action_bits<CF>(HL, VL, act_bits, dm);
-        next_act = nx;
-        draws = (f & (FLAG_TERMINAL | FLAG_BAD_ACTION)) ? 0 : step_draws;
-    }
-    if (legal) memcpy(legal, act_bits, sizeof(uint32_t) * dm.aw());
-    return r;
+    if (f & FLAG_RECOMPUTE) step_exact<CF>(P, a, i, recomputed, dm);
+    return paused;
 }
 
 static long g_paused = 0;  // steps that paused in the bounded-cascade mode (hc_paused)
-
-template <class CF, int CAP>
-static int step_small(typename CF::Bd* P, const int8_t* board, uint32_t seed, int na, int act, uint32_t& f,
-                      int32_t& draws, uint32_t* lg, int32_t& next_act, int& recomputed, const typename CF::Dim& dm) {
-    SmallStore<CF, CAP> ss;
-    return step_one<CF>(P, board, seed, na, act, ss, f, draws, lg, next_act, recomputed, dm);
-}
 
 template <class CF>
 static int apply_n(long n, const int8_t* boards, const uint32_t* seeds, const int32_t* nact, const int32_t* acts,
                    int8_t* out, int32_t* rew, int32_t* draws, int32_t* flags, uint32_t* legal, int32_t* next_act,
                    int small) {
     const auto dm = make_dim<CF>();
-    const int N = dm.cells(), AW = dm.aw();
+    m3k::ApplyArgs a{};  // the rows are the caller's arrays
+    a.n = n;
+    a.boards = boards;
+    a.seeds = seeds;
+    a.n_actions = nact;
+    a.actions = acts;
+    a.reward = rew;
+    a.draws = reinterpret_cast<uint32_t*>(draws);
+    a.flags = reinterpret_cast<uint32_t*>(flags);
+    a.legal = legal;
+    a.next_action = next_act;
     int recomputed = 0;
     for (long i = 0; i < n; ++i) {
         typename CF::Bd P[CF::NP];
-        const int8_t* bi = boards + i * N;
-        load_planes<CF>(bi, P, dm);
-        uint32_t f;
-        uint32_t* lg = legal ? legal + i * AW : nullptr;
+        load_planes<CF>(boards + i * dm.cells(), P, dm);
         if (small >= 100 && small < 120) {  // bounded cascade, paused after small - 100 iterations and resumed
             SmallStore<CF, 4> ss;
-            int paused = 0;
-            if (CF::N > 128)
-                rew[i] = step_one<CF, SmallStore<CF, 4>, ChainMT1>(P, bi, seeds[i], nact[i], acts[i], ss, f, draws[i],
-                                                                  lg, next_act[i], recomputed, dm, small - 100,
-                                                                  &paused);
-            else
-                rew[i] = step_one<CF>(P, bi, seeds[i], nact[i], acts[i], ss, f, draws[i], lg, next_act[i],
-                                      recomputed, dm, small - 100, &paused);
-            g_paused += paused;
-        } else if (small == 32) {  // the 16x16 / frame env step: one-level MT chain (< 227 draws) + 4-group table
+            g_paused += step_paused<CF>(P, a, i, ss, recomputed, dm, small - 100);
+        } else if (small == 32) {  // the env step's chain (16x16 / frame: one level, < 227 draws) + 4-group table
             SmallStore<CF, 4> ss;
-            rew[i] = step_one<CF, SmallStore<CF, 4>, ChainMT1>(P, bi, seeds[i], nact[i], acts[i], ss, f, draws[i],
-                                                              lg, next_act[i], recomputed, dm);
+            step_one<CF, typename KS<CF>::Chain>(P, a, i, ss, recomputed, dm);
         } else if (small == 8) {
-            rew[i] = step_small<CF, 8>(P, bi, seeds[i], nact[i], acts[i], f, draws[i], lg, next_act[i], recomputed, dm);
+            SmallStore<CF, 8> ss;
+            step_one<CF>(P, a, i, ss, recomputed, dm);
         } else if (small == 4) {
-            rew[i] = step_small<CF, 4>(P, bi, seeds[i], nact[i], acts[i], f, draws[i], lg, next_act[i], recomputed, dm);
+            SmallStore<CF, 4> ss;
+            step_one<CF>(P, a, i, ss, recomputed, dm);
         } else if (small) {
-            rew[i] = step_small<CF, 1>(P, bi, seeds[i], nact[i], acts[i], f, draws[i], lg, next_act[i], recomputed, dm);
+            SmallStore<CF, 1> ss;
+            step_one<CF>(P, a, i, ss, recomputed, dm);
         } else {
             ArrayStore<CF>* as = new ArrayStore<CF>;
-            rew[i] = step_one<CF>(P, bi, seeds[i], nact[i], acts[i], *as, f, draws[i], lg, next_act[i], recomputed, dm);
+            step_one<CF>(P, a, i, *as, recomputed, dm);
             delete as;
         }
-        flags[i] = (int32_t)(f & ~FLAG_RECOMPUTE);
-        store_planes<CF>(P, out + i * N, dm);
+        // apply_action's flags: FLAG_NO_LEGAL is apply_and_emit's own, for the next action it could
+        // not draw, which next_act = -1 reports here
+        flags[i] &= ~(int32_t)(FLAG_RECOMPUTE | FLAG_NO_LEGAL);
+        store_planes<CF>(P, out + i * dm.cells(), dm);
     }
     return recomputed;
 }
@@ -356,62 +361,54 @@ static void rounds_n(long n, const int8_t* boards, const uint32_t* seeds, const 
     }
 }
 
-// MCTS.rollout (mctslib/standard/mcts.py:14-19) the way k_rollout's rollout_one runs it: the first
-// choice on the rollout seed's chain, every step and later choice on the step seed's chain. Writes
-// gain, steps, draws (global-stream position when the rollout ends), flags; -1 gain when the chain
-// ran out (the kernel's k_rollout_fix replay). The group table is the full one (ArrayStore), so a
-// board with many groups (tests/crafted.py) is played here and not given up.
+// MCTS.rollout (mctslib/standard/mcts.py:14-19): k_rollout's rollout_one with k_rollout's chain
+// (KS<CF>::Chain), one board at a time. Writes gain, steps, draws (global-stream position when the
+// rollout ends), flags; -1 gain when the chain ran out (the kernel's k_rollout_fix replay). The group
+// table is the full one (ArrayStore), so a board with many groups (tests/crafted.py) is played here
+// and not given up.
 template <class CF>
 static void rollout_n(long n, const int8_t* boards, const uint32_t* seeds, const int32_t* nact, const uint32_t* rseeds,
                       int32_t* gain, int32_t* steps, uint32_t* draws, uint32_t* flags) {
     const auto dm = make_dim<CF>();
+    m3k::RolloutArgs a{};
+    a.n = n;
+    a.n_actions = nact;
+    a.gain = gain;
+    a.steps = steps;
+    a.draws = draws;
+    a.flags = flags;
+    ArrayStore<CF>* st = new ArrayStore<CF>;
     for (long i = 0; i < n; ++i) {
-        typename CF::Bd P[CF::NP], HL, VL;
+        typename CF::Bd P[CF::NP];
         load_planes<CF>(boards + i * dm.cells(), P, dm);
-        ChainMT first, rng;
+        typename KS<CF>::Chain first, rng;
         first.init(rseeds[i], mt_state397(rseeds[i]));
         rng.init(seeds[i], mt_state397(seeds[i]));
-        ArrayStore<CF> st;
-        int nn = nact[i], g = 0, s = 0;
-        uint32_t fl = 0u, dr = 0u;
-        bool ok = true;
-        if (nn >= 1) {
-            legal_masks<CF>(P, special_mask<CF, CF::NP>(P), HL, VL, dm);
-            uint32_t act[CF::AW];
-            action_bits<CF>(HL, VL, act, dm);
-            int x = random_action<CF>(act, first);
-            dr = first.draws();
-            for (;;) {
-                if (x < 0) {
-                    fl |= FLAG_NO_LEGAL;
-                    break;
-                }
-                uint32_t f;
-                const int r = apply_action<CF>(P, nn, x, rng, f, HL, VL, st, dm);
-                if (f & FLAG_RECOMPUTE) {
-                    ok = false;
-                    break;
-                }
-                fl |= f;
-                g += r;
-                ++s;
-                --nn;
-                dr = rng.draws();
-                if (nn < 1) break;
-                action_bits<CF>(HL, VL, act, dm);
-                x = random_action<CF>(act, rng);
-                if (rng.overflow) {
-                    ok = false;
-                    break;
-                }
-                dr = rng.draws();
-            }
-        }
-        gain[i] = ok ? g : -1;
-        steps[i] = s;
-        draws[i] = dr;
-        flags[i] = fl;
+        gain[i] = steps[i] = 0;
+        draws[i] = flags[i] = 0u;
+        if (!rollout_one<CF>(P, a, i, first, rng, *st, dm)) gain[i] = -1;
     }
+    delete st;
+}
+
+// what the kernels of a configuration are built with (hc_geometry)
+enum { GEO_GCAP, GEO_CHAIN_LIMIT, GEO_SPILL_RECORDS, GEO_FIX_LANES, GEO_NSLOT, GEO_RESET_KCAP, GEO_BPW,
+       GEO_CASCADE_LIMIT, GEO_SPILL_WORDS };
+template <class CF>
+static long geometry(int what) {
+    using K = KS<CF>;
+    switch (what) {
+        case GEO_GCAP: return K::GCAP;
+        case GEO_CHAIN_LIMIT: return K::CHAIN_LIMIT;
+        case GEO_SPILL_RECORDS: return K::SPILL_RECORDS;
+        case GEO_FIX_LANES: return FIX_GRID * (long)lanes_for<CF>();
+        case GEO_NSLOT: return NSLOT;
+        case GEO_RESET_KCAP: return RESET_KCAP;
+        case GEO_BPW: return K::BPW;
+        case GEO_CASCADE_LIMIT: return K::CASCADE_LIMIT;
+        case GEO_SPILL_WORDS: return SPILL_REC_WORDS<CF>;
+    }
+    return -1000;
 }
 
 using C9 = Cfg<9, 9, 6>;
@@ -548,6 +545,22 @@ int hc_rollout(int cfg, long n, const int8_t* b, const uint32_t* s, const int32_
     DISPATCH(cfg, CALL);
 #undef CALL
     return 0;
+}
+// one constant of the configuration's kernels (GEO_*); -1000: no such constant
+long hc_geometry(int cfg, int what) {
+    long rc = 0;
+#define CALL(CF) rc = geometry<CF>(what)
+    DISPATCH(cfg, CALL);
+#undef CALL
+    return rc;
+}
+// records of the spill pool of a launch of n rollouts
+long hc_rollout_spill_cap(int cfg, long n) {
+    long rc = 0;
+#define CALL(CF) rc = (long)rollout_spill_cap(n, (size_t)SPILL_REC_WORDS<CF>)
+    DISPATCH(cfg, CALL);
+#undef CALL
+    return rc;
 }
 long hc_paused(int reset) {
     const long v = g_paused;

@@ -1,35 +1,29 @@
 """ctypes face of the TEST-ONLY host build of the device rule code (hostcore.hip)."""
 import ctypes
 import os
-import subprocess
+import sys
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+from hostbuild import build  # noqa: E402
+
 LIB = os.path.join(HERE, "libhostcore.so")
-SRC = [os.path.join(HERE, "hostcore.hip")] + [
-    os.path.join(HERE, "..", "..", "element-crush-gym_amd", "csrc", f) for f in
-    ("m3_rules.hpp", "m3_bitboard.hpp", "m3_rng.hpp")]
 _lib = None
 CFG_ID = {(9, 9, 6): 0, (16, 16, 8): 1}
 FRAME = 2  # any other shape, in its frame (16 x 16, or 32 x 32 for a side > 16; hc_set_frame)
-
-
-def build():
-    newest = max(os.path.getmtime(s) for s in SRC)
-    if os.path.exists(LIB) and os.path.getmtime(LIB) >= newest:
-        return
-    # -O0: the 32 x 32-frame instantiations take ~30 min to optimise on the host (1024-bit planes,
-    # fully unrolled); unoptimised, the whole harness builds in ~2 min and the tests still run in seconds
-    subprocess.run(["hipcc", "--offload-arch=gfx950", "-O0", "-std=c++17", "-fPIC", "-shared",
-                    "-o", LIB + ".tmp", SRC[0]], check=True)
-    os.replace(LIB + ".tmp", LIB)
+# hc_geometry's `what` (the GEO_* of hostcore.hip): constants the configuration's kernels are built with
+GEOMETRY = ("GCAP", "CHAIN_LIMIT", "SPILL_RECORDS", "FIX_LANES", "NSLOT", "RESET_KCAP", "BPW", "CASCADE_LIMIT",
+            "SPILL_WORDS")
 
 
 def lib():
     global _lib
     if _lib is None:
-        build()
+        # -O0: the 32 x 32-frame instantiations take ~30 min to optimise on the host (1024-bit planes,
+        # fully unrolled); unoptimised, the whole harness builds in ~2 min and the tests still run in seconds
+        build(LIB, os.path.join(HERE, "hostcore.hip"), ["-O0"])
         _lib = ctypes.CDLL(LIB)
         _lib.hc_chain_draw.restype = ctypes.c_uint32
         _lib.hc_chain_draw.argtypes = [ctypes.c_uint32, ctypes.c_int]
@@ -37,6 +31,10 @@ def lib():
         _lib.hc_mask_mismatches.argtypes = [ctypes.c_int, ctypes.c_long, ctypes.c_void_p]
         _lib.hc_fast_match_mismatches.restype = ctypes.c_long
         _lib.hc_fast_match_mismatches.argtypes = [ctypes.c_int, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p]
+        _lib.hc_geometry.restype = ctypes.c_long
+        _lib.hc_geometry.argtypes = [ctypes.c_int, ctypes.c_int]
+        _lib.hc_rollout_spill_cap.restype = ctypes.c_long
+        _lib.hc_rollout_spill_cap.argtypes = [ctypes.c_int, ctypes.c_long]
     return _lib
 
 
@@ -59,6 +57,17 @@ class HostCore:
     def _sel(self):
         if self.frame:
             assert lib().hc_set_frame(*self.shape) == 0, self.shape
+
+    def geometry(self):
+        """{name: value} of GEOMETRY for the configuration this shape runs in (KS<CF> and its
+        neighbours in m3_batch_core.hpp, as compiled); FIX_LANES = FIX_GRID x lanes_for<CF>()"""
+        self._sel()
+        return {k: lib().hc_geometry(self.cfg, i) for i, k in enumerate(GEOMETRY)}
+
+    def rollout_spill_cap(self, n):
+        """rollout_spill_cap(n, the configuration's spill-record words)"""
+        self._sel()
+        return lib().hc_rollout_spill_cap(self.cfg, n)
 
     def apply(self, boards, seeds, n_actions, actions, small=False):
         boards = np.ascontiguousarray(boards, dtype=np.int8).reshape(-1, self.N)
@@ -122,7 +131,7 @@ class HostCore:
 
 
     def rollouts(self, boards, seeds, n_actions, rseeds):
-        """rollout_one of k_rollout on the CPU (gain -1: the chain ran out, the kernel's replay case)"""
+        """rollout_one with k_rollout's chain on the CPU (gain -1: the chain ran out, the kernel's replay case)"""
         boards = np.ascontiguousarray(boards, dtype=np.int8).reshape(-1, self.N)
         n = len(boards)
         seeds = np.ascontiguousarray(np.broadcast_to(seeds, (n,)), dtype=np.uint32)

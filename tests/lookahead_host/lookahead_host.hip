@@ -6,6 +6,7 @@
 //
 // cfg 0 = Cfg<9,9,6>, cfg 1 = Cfg<16,16,8>, cfg 2 = the 16 x 16 frame for the shape set by
 // lh_set_frame (the lookahead is not built for the 32 x 32 frame).
+#include "../../element-crush-gym_amd/csrc/m3_batch_core.hpp"  // KS: the table and the chain the kernels use
 #include "../../element-crush-gym_amd/csrc/m3_lookahead_core.hpp"
 
 #include <stdlib.h>
@@ -17,15 +18,6 @@ using namespace m3;
 
 static int g_T = 6;
 static Shape g_shape = make_shape(9, 9, 6);
-
-// KS<CF>::GCAP and KS<CF>::Chain of m3_kernels.hpp (the test holds lh_gcap / lh_chain_limit to
-// tests/crafted.py, which test_crafted_cpu pins to the source)
-template <class CF>
-struct HK {
-    static constexpr int GCAP = CF::N <= 128 ? 6 : 4;
-    using Chain = std::conditional_t<(CF::N > 128), ChainMT1, ChainMT>;
-    static constexpr int LIMIT = CF::N > 128 ? 227 : 624;
-};
 
 template <class CF>
 static void load_planes(const int8_t* b, typename CF::Bd* P, const typename CF::Dim& dm) {
@@ -60,7 +52,7 @@ static int lookahead_n(int bpw, long n, const int8_t* boards, const uint32_t* se
     std::vector<uint32_t> act_s((size_t)bpw * CF::AW), pre_s(bpw + 1), m397_s(bpw);
     std::vector<LookAcc> acc_s(bpw);
     std::vector<long> redo;
-    auto* st = new SmallStore<CF, HK<CF>::GCAP>;
+    auto* st = new SmallStore<CF, KS<CF>::GCAP>;
     for (long b0 = 0; b0 < n; b0 += bpw) {
         const int nb = (int)((n - b0) < bpw ? (n - b0) : bpw);
         uint32_t run = 0;
@@ -90,7 +82,7 @@ static int lookahead_n(int bpw, long n, const int8_t* boards, const uint32_t* se
                 if (action < 0 || action >= A) return -3;
                 typename CF::Bd P[CF::NP];
                 load_planes<CF>(boards + (b0 + g) * NC, P, dm);
-                const LookCand c = look_eval<CF, typename HK<CF>::Chain>(P, seeds[b0 + g], m397_s[g], nact[b0 + g],
+                const LookCand c = look_eval<CF, typename KS<CF>::Chain>(P, seeds[b0 + g], m397_s[g], nact[b0 + g],
                                                                         action, *st, dm);
                 if (values && !c.redo) values[(b0 + g) * A + action] = c.reward;
                 look_fold(&acc_s[g], c, action, j + 1u == pre_s[g + 1]);
@@ -178,7 +170,7 @@ int lh_lookahead(int cfg, int bpw, long n, const int8_t* boards, const uint32_t*
 
 int lh_gcap(int cfg) {
     int rc = 0;
-#define CALL(CF) rc = HK<CF>::GCAP
+#define CALL(CF) rc = KS<CF>::GCAP
     LH_DISPATCH(cfg, CALL);
 #undef CALL
     return rc;
@@ -186,7 +178,7 @@ int lh_gcap(int cfg) {
 
 int lh_chain_limit(int cfg) {
     int rc = 0;
-#define CALL(CF) rc = HK<CF>::LIMIT
+#define CALL(CF) rc = KS<CF>::CHAIN_LIMIT
     LH_DISPATCH(cfg, CALL);
 #undef CALL
     return rc;

@@ -1,28 +1,18 @@
 """ctypes face of the TEST-ONLY host build of the lookahead core (lookahead_host.hip)."""
 import ctypes
 import os
-import subprocess
+import sys
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+from hostbuild import build  # noqa: E402
+
 LIB = os.path.join(HERE, "liblookahead_host.so")
-SRC = [os.path.join(HERE, "lookahead_host.hip")] + [
-    os.path.join(HERE, "..", "..", "element-crush-gym_amd", "csrc", f) for f in
-    ("m3_lookahead_core.hpp", "m3_rules.hpp", "m3_bitboard.hpp", "m3_rng.hpp")]
 _lib = None
 CFG_ID = {(9, 9, 6): 0, (16, 16, 8): 1}
 FRAME = 2  # any other shape with sides up to 16, in the 16 x 16 frame (lh_set_frame)
-
-
-def build():
-    newest = max(os.path.getmtime(s) for s in SRC)
-    if os.path.exists(LIB) and os.path.getmtime(LIB) >= newest:
-        return
-    # the recipe of tests/hostcore/hostcore.py (-O0: the frame instantiations optimise slowly on the host)
-    subprocess.run(["hipcc", "--offload-arch=gfx950", "-O0", "-std=c++17", "-fPIC", "-shared",
-                    "-o", LIB + ".tmp", SRC[0]], check=True)
-    os.replace(LIB + ".tmp", LIB)
 
 
 def _p(a):
@@ -32,7 +22,8 @@ def _p(a):
 def lib():
     global _lib
     if _lib is None:
-        build()
+        # -O0, as tests/hostcore (the frame instantiations optimise slowly on the host)
+        build(LIB, os.path.join(HERE, "lookahead_host.hip"), ["-O0"])
         L = ctypes.CDLL(LIB)
         vp, i32, u32, u64, lg = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_long
         L.lh_lookahead.argtypes = [i32, i32, lg] + [vp] * 9

@@ -1,27 +1,18 @@
 """ctypes face of the TEST-ONLY host build of the 9x9x6 refill (refill_host.hip)."""
 import ctypes
 import os
-import subprocess
+import sys
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+from hostbuild import build  # noqa: E402
+
 LIB = os.path.join(HERE, "librefill_host.so")
-SRC = [os.path.join(HERE, "refill_host.hip")] + [
-    os.path.join(HERE, "..", "..", "element-crush-gym_amd", "csrc", f) for f in
-    ("m3_rules.hpp", "m3_bitboard.hpp", "m3_rng.hpp")]
 _lib = None
 R = C = 9
 NP, W = 7, 3
-
-
-def build():
-    newest = max(os.path.getmtime(s) for s in SRC)
-    if os.path.exists(LIB) and os.path.getmtime(LIB) >= newest:
-        return
-    subprocess.run(["hipcc", "--offload-arch=gfx950", "--offload-host-only", "-O1", "-std=c++17", "-fPIC", "-shared",
-                    "-o", LIB + ".tmp", SRC[0]], check=True)
-    os.replace(LIB + ".tmp", LIB)
 
 
 def _p(a):
@@ -31,7 +22,7 @@ def _p(a):
 def lib():
     global _lib
     if _lib is None:
-        build()
+        build(LIB, os.path.join(HERE, "refill_host.hip"), ["--offload-host-only", "-O1"])
         L = ctypes.CDLL(LIB)
         vp, i32, lg = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
         L.rf_refill.argtypes = [i32, i32, lg] + [vp] * 6

@@ -2,24 +2,16 @@
 that plays the kernels' rounds with the C oracle's step and playout in between."""
 import ctypes
 import os
-import subprocess
+import sys
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+from hostbuild import build  # noqa: E402
+
 LIB = os.path.join(HERE, "libsearch_host.so")
-SRC = [os.path.join(HERE, "search_host.hip"),
-       os.path.join(HERE, "..", "..", "element-crush-gym_amd", "csrc", "m3_search_core.hpp")]
 _lib = None
-
-
-def build():
-    newest = max(os.path.getmtime(s) for s in SRC)
-    if os.path.exists(LIB) and os.path.getmtime(LIB) >= newest:
-        return
-    subprocess.run(["hipcc", "--offload-arch=gfx950", "--offload-host-only", "-O1", "-std=c++17", "-fPIC", "-shared",
-                    "-o", LIB + ".tmp", SRC[0]], check=True)
-    os.replace(LIB + ".tmp", LIB)
 
 
 def _p(a):
@@ -29,7 +21,7 @@ def _p(a):
 def lib():
     global _lib
     if _lib is None:
-        build()
+        build(LIB, os.path.join(HERE, "search_host.hip"), ["--offload-host-only", "-O1"])
         L = ctypes.CDLL(LIB)
         vp, i32, lg = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
         L.sh_create.argtypes, L.sh_create.restype = [lg, i32, i32, i32, i32], vp

@@ -3,14 +3,13 @@ their input, from the oracle alone -- so that none of them can pass because its 
 and the host build of the device rule code (tests/hostcore) on the same rows: many-group scans,
 merges into late groups and full-board refills before any of it runs on a GPU."""
 import os
-import re
 import sys
 
 import numpy as np
 import pytest
 
 import crafted
-from conftest import PKG, ROOT, SHAPES
+from conftest import ROOT, SHAPES
 from oracle import FLAG_SHUFFLED, Oracle
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "hostcore"))
@@ -20,21 +19,35 @@ ALL = dict(SHAPES, **{"8x8x5": (8, 8, 5)})  # (the frame shape of the GPU tests)
 
 
 def test_constants_match_the_kernel_source():
-    """crafted.lcap / chain_limit restate KS::GCAP and KS::Chain (m3_kernels.hpp), the pool sizes
-    of test_gpu_fallbacks restate SPILL_RECORDS and rollout_spill_cap: held to the source text."""
-    src = open(os.path.join(PKG, "csrc", "m3_kernels.hpp")).read()
-    assert re.search(r"GCAP = CF::N <= 128 \? 6 : 4;", src)
-    assert re.search(r"using Chain = std::conditional_t<\(CF::N > 128\), ChainMT1, ChainMT>;", src)
-    assert re.search(r"SPILL_RECORDS = CF::W > 8 \? 256 : 4096;", src)
-    assert re.search(r"constexpr int FIX_GRID = 16;", src)
-    assert re.search(r"#define M3_NSLOT 4\n", src)
-    rng = open(os.path.join(PKG, "csrc", "m3_rng.hpp")).read()
-    assert "using ChainMT = ChainMTT<624u>;" in rng and "using ChainMT1 = ChainMTT<227u>;" in rng
-    # a frame shape runs in FCfg, whose N is the frame's 256 or 1024 cells whatever the board's
-    assert re.search(r"struct FCfg \{\n    static constexpr bool DYN = true;\n    static constexpr int FS = FS_;", open(
-        os.path.join(PKG, "csrc", "m3_rules.hpp")).read())
-    assert [crafted.lcap(s) for s in ((9, 9, 6), (16, 16, 8), (8, 8, 5), (9, 9, 5))] == [6, 4, 4, 4]
-    assert [crafted.chain_limit(s) for s in ((9, 9, 6), (16, 16, 8), (8, 8, 5))] == [624, 227, 227]
+    """Every kernel constant that tests/crafted.py restates for the GPU tests -- KS::GCAP, the reach of
+    KS::Chain, the pool sizes, the fix kernels' lanes, NSLOT, RESET_KCAP -- against the value compiled
+    into the host harness from the kernels' own header (hc_geometry), for each kind of configuration:
+    the two specialised shapes, the 16 x 16 frame and the 32 x 32 frame."""
+    # (8, 8, 5) and (9, 9, 5) run in FCfg, whose N is the frame's 256 cells whatever the board's: a
+    # table or chain sized by the board's own cells (9x9x5: 81, as 9x9x6) would show in these two rows
+    shapes = ((9, 9, 6), (16, 16, 8), (8, 8, 5), (9, 9, 5), (20, 20, 6))
+    for shape in shapes:
+        hc = HostCore(*shape)
+        g = hc.geometry()
+        assert crafted.lcap(shape) == g["GCAP"], shape
+        assert crafted.chain_limit(shape) == g["CHAIN_LIMIT"], shape
+        assert crafted.pool(shape) == g["SPILL_RECORDS"], shape
+        assert crafted.fix_lanes(shape) == g["FIX_LANES"], shape
+        assert crafted.NSLOT == g["NSLOT"], shape
+        assert crafted.RESET_KCAP_9 == g["RESET_KCAP"], shape
+        assert g["BPW"] == (1 if shape == (20, 20, 6) else 64), shape
+        assert g["CASCADE_LIMIT"] == (2 if shape == (9, 9, 6) else -1), shape  # (test_hostcore_cpu's pauses)
+        for n in (8192, 65536):
+            budget = (256 << 20) // (4 * g["SPILL_WORDS"])
+            want = crafted.rollout_pool(n) if shape != (20, 20, 6) else min(crafted.rollout_pool(n), budget)
+            assert hc.rollout_spill_cap(n) == want, (shape, n)
+            assert shape == (20, 20, 6) or budget > want, (shape, n)  # (rollout_pool's premise)
+    # what the GPU tests use outright, for the shapes they run
+    for shape in ALL.values():
+        assert (crafted.pool(shape), crafted.fix_lanes(shape)) == (crafted.POOL, crafted.FIX_LANES)
+    assert crafted.rollout_pool(8192) == crafted.POOL
+    assert [crafted.lcap(s) for s in shapes[:4]] == [6, 4, 4, 4]
+    assert [crafted.chain_limit(s) for s in shapes[:3]] == [624, 227, 227]
 
 
 @pytest.mark.parametrize("tag", list(ALL))

@@ -27,9 +27,9 @@ from oracle import Oracle  # noqa: E402
 BIG = 2**31 - 1
 MOVES = 3           # episode length of the env cases: a third of the rows finish on the crafted step
 STRIDE = 1 << 20    # autoreset seed increment
-POOL = 4096         # KS::SPILL_RECORDS per shard and step; rollout_spill_cap for n <= 32768
-FIX_LANES = 1024    # FIX_GRID x 64: the fix kernels' lanes; more work takes their grid-stride loop
-EXTRA = 4           # steps after the crafted one: NSLOT, one more than the prefetch queues are deep
+POOL = crafted.POOL            # KS::SPILL_RECORDS per shard and step; rollout_spill_cap for n <= 32768
+FIX_LANES = crafted.FIX_LANES  # the fix kernels' lanes; more work takes their grid-stride loop
+EXTRA = crafted.NSLOT          # steps after the crafted one: one more than the prefetch queues are deep
 
 ALL = dict(SHAPES, **{"8x8x5": (8, 8, 5)})  # (8x8x5: a frame shape -- the 16x16x8 table and chain)
 

@@ -8,6 +8,7 @@ properties at 1,048,576 boards (C3).
 import numpy as np
 import pytest
 
+import crafted
 from conftest import SHAPES
 
 pytestmark = pytest.mark.gpu
@@ -206,8 +207,8 @@ def test_autoreset_matches_fresh_episodes(tag):
     env.close()
 
 
-RESET_KCAP_9 = 454  # k_init<CF, false> gives up a prefetched 9x9x6 reset past this many draws (m3_kernels.hpp)
-NSLOT = 4           # episode slots per board (m3_kernels.hpp): a freed slot takes the episode NSLOT - 1 ahead
+RESET_KCAP_9 = crafted.RESET_KCAP_9  # k_init<CF, false> gives up a prefetched 9x9x6 reset past this many draws
+NSLOT = crafted.NSLOT                # episode slots per board: a freed slot takes the episode NSLOT - 1 ahead
 
 
 @pytest.mark.parametrize("tag", list(SHAPES))
