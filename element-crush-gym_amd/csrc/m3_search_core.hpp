@@ -54,6 +54,10 @@ namespace m3s {
 constexpr uint32_t SF_BAD_ACTION = 0x02u, SF_SHUFFLE_CAP = 0x04u, SF_NO_LEGAL = 0x08u, SF_CASCADE_CAP = 0x100u;
 // what freezes a game: the reference raises (max() of no children, np.random.choice([])) or never returns
 constexpr uint32_t SF_FREEZE = SF_SHUFFLE_CAP | SF_NO_LEGAL | SF_CASCADE_CAP;
+// what freezes a game in an expansion's step: the caps only. The apply launch also samples the action
+// after the step and sets NO_LEGAL when the board it left has none (m3_apply_actions' next_action);
+// the search samples nothing there -- the reference is still shuffling -- so that bit is not the game's.
+constexpr uint32_t SF_STEP_FREEZE = SF_SHUFFLE_CAP | SF_CASCADE_CAP;
 
 struct SNodeHot {
     int64_t reward_sum;  // Node.reward
@@ -203,8 +207,8 @@ M3_HD int32_t search_attach(const STree& T, int64_t g, int32_t step_reward, uint
     if (T.gflags[g]) return 0;
     const int32_t leaf = T.leaf[g];
     if (!T.expanded[g]) return T.link[base + leaf].n_actions;
-    if (step_flags & SF_FREEZE) {
-        T.gflags[g] |= step_flags & SF_FREEZE;
+    if (step_flags & SF_STEP_FREEZE) {
+        T.gflags[g] |= step_flags & SF_STEP_FREEZE;
         return 0;
     }
     const int32_t child = T.used[g]++;  // (the host checked the capacity before the run)

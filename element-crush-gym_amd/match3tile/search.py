@@ -14,6 +14,18 @@ generator, root re-use between calls. So game g returns what ``MCTS(states[g], c
 rng=rngs[g])()`` returns. (The reference's ``exploration_weight`` argument is not read by its
 selection, abc/mcts.py:96, and has no counterpart here.)
 
+One departure, kept on purpose: a root that is already terminal (``n_actions < 1``) when the trees are
+built. The reference's constructor expands unconditionally (abc/mcts.py:82), ``apply_action`` of a
+terminal state returns the state itself, and ``MCTS(...)()`` answers with an unplayable action and
+the policy ``[0.0]``. Here such a root keeps no child: ``result()`` reports ``best_action`` -1, no
+children, ``value`` = the root's reward, and the simulations in ``root_visits``; ``__call__`` raises
+``ValueError``, as it does -- there like the reference, whose last lines raise -- for a root that
+became terminal by re-rooting. ``dataset.play_games`` never builds such a root.
+
+A game freezes (include/m3.h) where the reference raises or never returns; ``result()["flags"]`` holds
+its ``M3_FLAG_*`` word, its tree stays as it stood, and the games beside it go on. Board shapes with a
+side above 16 (the 32 x 32 frame of the kernels) are searched like any other.
+
 ``leaf_rollouts > 1`` and ``deterministic=True`` stay on the host path (``match3tile.mcts.MCTS``).
 
 numpy's global RNG: the reference leaves it where the last rollout's last ``apply_action`` left it.
@@ -145,16 +157,20 @@ class DeviceSearch:
         """``simulations`` rounds for every game, then re-root at the best action, as ``MCTS.__call__``.
         Returns [(action, value, policies)] per game; policies = child visits / root visits in
         expansion order. ValueError where ``rollouts()`` raises (a state without a legal action),
-        RuntimeError where a step or a rollout stopped at a shuffle or cascade cap."""
+        RuntimeError where a step or a rollout stopped at a shuffle or cascade cap (the cap decides for
+        a game that holds both; a game of the first kind anywhere in the batch is reported first)."""
         if any(s.is_terminal for s in self._states):
-            raise ValueError("search of a terminal state (the reference's MCTS.__call__ raises in its last lines)")
+            raise ValueError("search of a terminal state (after a re-rooting the reference's MCTS.__call__ raises in its "
+                             "last lines; a root that was terminal from the start has no child here: see the module docstring)")
         seeds = np.empty((self.simulations, self.n), np.uint32)
         for g, rng in enumerate(self._rngs):  # game by game: each game's seeds in order from its own generator
             seeds[:, g] = [rng.randint(0, SEED_BOUND) for _ in range(self.simulations)]
         self.run(seeds)
         res = self.result(children=False)
         fl = res["flags"]
-        if (fl & _native.FLAG_NO_LEGAL).any():
+        # (a playout that stopped at a cap finds no legal action at its next move: that game's
+        # M3_FLAG_NO_LEGAL comes from the cap, where the reference is still shuffling)
+        if ((fl & _native.FLAG_NO_LEGAL != 0) & (fl & _CAPS == 0)).any():
             raise ValueError("a search reached a board with no legal action (np.random.choice of an empty list)")
         if (fl & _CAPS).any():
             raise RuntimeError("a step or a rollout of the search stopped at a shuffle or cascade cap "

@@ -169,7 +169,14 @@ int m3_lookahead_device(m3_ctx *ctx, int64_t n, const int8_t *boards, const uint
  * A game freezes -- no expansion, no backup for the rest of its life, its flag word set -- where the
  * reference raises or never returns: a non-terminal node without a legal action (M3_FLAG_NO_LEGAL:
  * max() of no children, abc/mcts.py:96) and M3_FLAG_SHUFFLE_CAP / M3_FLAG_CASCADE_CAP of a step or a
- * rollout. The other games go on. */
+ * rollout (an expansion's step gives its cap bits only: nothing is sampled after it; a rollout gives
+ * its whole word, M3_FLAG_NO_LEGAL included where it went on past a cap to its next choice).
+ * The other games go on. A frozen game's result is its root's children and visits as they
+ * stood and its flag word (value: the root's reward, no part of the contract); m3_search_advance
+ * leaves its root where it is and does not count it as a bad action.
+ *
+ * Every board shape the context takes is searched, the 32 x 32 frame (a side above 16) included:
+ * unlike m3_lookahead, m3_search_create refuses none of them but rows < columns (M3_ERR_INVALID). */
 int m3_search_create(m3_ctx *ctx, int64_t n_games, int32_t node_capacity, m3_search **out);
 int m3_search_destroy(m3_search *s);
 /* out[v - 1] = log(v) for v = 1..n: the table UCB1's log(parent.visits) is read from, std::log of
@@ -177,7 +184,13 @@ int m3_search_destroy(m3_search *s);
 int m3_search_log_table(int32_t n, double *out);
 /* MCTS.__init__ (abc/mcts.py:78-82) for every game: the root node of state (boards[i], cfg.seed =
  * seeds[i], n_actions[i], reward = rewards[i]) and the constructor's one expansion, without a
- * rollout. Drops the trees the object held. Host buffers; blocks until done. */
+ * rollout. Drops the trees the object held: node slots, flag words and statistics start again.
+ * Host buffers; blocks until done.
+ * One departure from the reference, on purpose: a root with n_actions < 1. The reference's
+ * constructor expands it all the same, apply_action of a terminal state returns the state itself,
+ * and its search answers with an unplayable action and the policy [0.0]. Here such a root keeps no
+ * child: m3_search_result reports best_action -1, n_children 0, value = rewards[i], flags 0, and
+ * root_visits counts the simulations run. */
 int m3_search_set_roots(m3_search *s, const int8_t *boards, const uint32_t *seeds, const int32_t *n_actions,
                         const int32_t *rewards);
 /* `simulations` rounds of MCTS.__call__'s loop (abc/mcts.py:91-109) for every game. rollout_seeds:

@@ -102,6 +102,29 @@ def first_scan_groups(o: Oracle, board, action=None, dec=None):
     return o.get_matches(b & o.cfg.TM)[2]
 
 
+def first_scan_takes_table(o: Oracle, board, action=None, dec=None):
+    """Whether the step's first get_matches goes through the sequential scan and its group table at
+    all (m3_rules.hpp, get_matches): only with a cell in both a horizontal and a vertical run of three
+    or more, or with a run of six or more. Without either every maximal run is its own group and no
+    table is filled, however many groups there are -- a swap that takes a cell out of the painted
+    plus leaves such a board."""
+    b = np.array(board, np.int32)
+    if action is not None:
+        sr, sc, tr, tc = (dec if dec is not None else decode_table(o))[action]
+        b[sr, sc], b[tr, tc] = b[tr, tc], b[sr, sc]
+    b &= o.cfg.TM
+    R, C = b.shape
+    h3 = (b[:, :-2] != 0) & (b[:, :-2] == b[:, 1:-1]) & (b[:, 1:-1] == b[:, 2:])  # a horizontal triple starts here
+    v3 = (b[:-2] != 0) & (b[:-2] == b[1:-1]) & (b[1:-1] == b[2:])
+    hc, vc = np.zeros((R, C), bool), np.zeros((R, C), bool)
+    for k in range(3):
+        hc[:, k:C - 2 + k] |= h3
+        vc[k:R - 2 + k] |= v3
+    six = ((h3[:, :-3] & h3[:, 1:-2] & h3[:, 2:-1] & h3[:, 3:]).any() if C >= 6 else False) or \
+          ((v3[:-3] & v3[1:-2] & v3[2:-1] & v3[3:]).any() if R >= 6 else False)
+    return bool((hc & vc).any() or six)
+
+
 def _paint(board, used, cells, rng, T):
     """Paint `cells` in one colour that no outside neighbour has; False if they are taken or no
     colour is left."""

@@ -56,10 +56,16 @@ class HostSearch:
         self.o, self.n, self.cap = oracle, len(states), int(node_capacity)
         self.N, self.A = oracle.R * oracle.C, oracle.A
         self.AW = (self.A + 31) // 32
-        self.seeds = [int(s.cfg.seed) for s in states]
         self.h = lib().sh_create(self.n, self.cap, self.N, self.AW, self.A)
         self.rec = record
         self._rec([self.n, self.cap, self.N, self.AW, self.A])
+        self.set_roots(states)
+
+    def set_roots(self, states):
+        """m3_search_set_roots: as many states as the object has games; the trees it held are dropped."""
+        oracle = self.o
+        assert len(states) == self.n
+        self.seeds = [int(s.cfg.seed) for s in states]
         boards = np.ascontiguousarray(np.stack([np.asarray(s.array).reshape(-1) for s in states]), dtype=np.int8)
         na = np.array([s.n_actions for s in states], np.int32)
         rew = np.array([s.reward for s in states], np.int32)
@@ -90,8 +96,11 @@ class HostSearch:
             if row_na[g] >= 1:
                 nb, r, _, f = self.o.apply_action(rows[g].astype(np.int32).reshape(self.o.R, self.o.C), self.seeds[g],
                                                   int(row_act[g]), int(row_na[g]))
+                legal = self.o.legal_actions(nb)
+                if not legal:  # as k_apply: it samples the action after the step, and flags an empty set
+                    f |= 0x08
                 ob[g], rew[g], fl[g] = np.asarray(nb).reshape(-1), r, f
-                lg[g] = actions_to_bits(self.o.legal_actions(nb), self.AW)
+                lg[g] = actions_to_bits(legal, self.AW)
         ro = np.zeros((n, N), np.int8)
         ro_na = np.zeros(n, np.int32)
         self._rec([2 if rseeds is None else 4], ob, rew, fl, lg)

@@ -1,7 +1,11 @@
 """Expected side of the device-tree tests: ``match3tile.mcts.MCTS`` over the C oracle (the pairing
 tests/test_mcts_cpu.py pins to the real reference's outputs), one search per root, with everything a
 tree holds at the end of each call -- not only (action, value, policies) but every root child's
-visits and reward sum -- and the rollout seeds each call drew, in order."""
+visits and reward sum -- and the rollout seeds each call drew, in order.
+
+reference_search starts at a reset board and never freezes. general_search starts at any root state
+(board, cfg seed, n_actions, reward), re-roots at a child of the caller's choice, and freezes a game
+where include/m3.h says the library does; the cases the CPU and the GPU tests share are built on it."""
 import os
 import random
 import sys
@@ -78,6 +82,218 @@ def assert_result(res, g, want, tag=""):
     assert got == [(int(a), int(v), int(r)) for a, v, r in want["children"]], (tag, g)
     pol = [int(res["child_visits"][g][j]) / int(res["root_visits"][g]) for j in range(k)]
     assert pol == list(want["policies"]), (tag, g)
+
+
+# ---- the general, freeze-aware expected side -------------------------------------------------
+# include/m3.h: a game freezes where the reference raises or never returns, and the other games go on.
+# The reference itself cannot say "never returns", so its states raise where the oracle reports it:
+# the oracle here stops a dead-board shuffle at the kernels' cap of 1,024 in the playouts as well.
+F_SHUFFLE_CAP, F_NO_LEGAL, F_CASCADE_CAP = 0x04, 0x08, 0x100
+F_STEP_FREEZE = F_SHUFFLE_CAP | F_CASCADE_CAP
+F_FREEZE = F_SHUFFLE_CAP | F_NO_LEGAL | F_CASCADE_CAP
+
+_capped = {}
+
+
+def capped_oracle(shape):
+    """The oracle with the shuffle cap of the kernels (1,024) in its playouts too."""
+    if shape not in _capped:
+        _capped[shape] = Oracle(*shape, episode_shuffle_cap=1024)
+    return _capped[shape]
+
+
+class Freeze(Exception):
+    def __init__(self, flags):
+        super().__init__(hex(flags))
+        self.flags = flags
+
+
+class FreezingBoard(OracleBoard):
+    """OracleBoard whose apply_action raises where the oracle's step stopped at a cap."""
+
+    def apply_action(self, a):
+        if self.is_terminal:
+            return self
+        nb, r, _, f = self._o.apply_action(self.array, self.cfg.seed, a, self.n_actions)
+        if f & F_STEP_FREEZE:
+            raise Freeze(f & F_FREEZE)
+        return FreezingBoard(self.n_actions - 1, self.cfg, self._o, nb, self._reward + r)
+
+    def clone(self):
+        c = FreezingBoard(self.n_actions, self.cfg, self._o, np.copy(self.array), self._reward)
+        c._actions = self._actions
+        return c
+
+
+def freezing_rollouts(o):
+    def run(states, seeds):
+        res = o.rollouts(np.stack([s.array for s in states]), [s.cfg.seed for s in states],
+                         [s.n_actions for s in states], seeds, threads=1)
+        fl = int(np.bitwise_or.reduce(res["flags"])) & F_FREEZE
+        if fl:
+            raise Freeze(fl)
+        return np.array([s.reward for s in states]) + res["gain"]
+    return run
+
+
+def state(shape, board, seed, n_actions, reward=0):
+    """A root over the capped oracle: board [rows, columns] (None: the reset board of `seed`)."""
+    o = capped_oracle(shape)
+    cfg = BoardConfig(rows=shape[0], columns=shape[1], types=shape[2], seed=int(seed))
+    arr = None if board is None else np.array(board, np.int32).reshape(shape[0], shape[1])
+    return FreezingBoard(int(n_actions), cfg, o, arr, int(reward))
+
+
+def _raised_no_child(e):
+    """best_child over no children returns None, and the next line reads None.state / None.parent."""
+    return isinstance(e, AttributeError) and "NoneType" in str(e)
+
+
+def general_search(shape, board, seed, n_actions, reward, sims, pyseed, calls, pick=None):
+    """The reference's search from any root state, freezing as the library does.
+
+    Returns ([per call: dict(children=[(action, visits, reward_sum)], root_visits, flags) and, where
+    flags == 0, action, value, policies, next=(n_actions, reward) of the root the call re-roots at],
+    the rollout seeds [calls][sims] of the game's generator random.Random(pyseed)).
+
+    pick(call, result) -> action chooses the child to re-root at (default: the result's action); it is
+    part of the cache key, so pass a module-level function. A game that freezes -- a cap in an
+    expansion's step or in a playout, pop() of an empty untried list or best_child over no children
+    (0x08) -- reports the root's children and visits as they stood at the exception, and those flag
+    bits, for that call and every later one. A root with n_actions < 1 is the library's documented
+    departure (include/m3.h, m3_search_set_roots): no child, action -1, value = reward, the
+    simulations counted in root_visits, flags 0."""
+    arr = None if board is None else np.array(board, np.int32).reshape(shape[0], shape[1])
+    key = ("general", shape, None if arr is None else arr.tobytes(), int(seed), int(n_actions), int(reward), sims, pyseed,
+           calls, pick)
+    if key in _cache:
+        return _cache[key]
+    seeds = rollout_seeds(pyseed, sims, calls)
+    out = []
+    if n_actions < 1:
+        for call in range(calls):
+            out.append(dict(children=[], root_visits=sims * (call + 1), flags=0, action=-1, value=int(reward), policies=[],
+                            next=None))
+        _cache[key] = (out, seeds)
+        return _cache[key]
+    frozen, m = None, None
+    try:
+        m = MCTS(state(shape, arr, seed, n_actions, reward), 3.0, sims, False,
+                 rollout_fn=freezing_rollouts(capped_oracle(shape)), rng=random.Random(pyseed))
+    except Freeze as e:  # the constructor's expansion: the root has no child yet
+        frozen = dict(children=[], root_visits=0, flags=e.flags, where="step")
+    except IndexError:   # pop() of an empty list: a root that is not terminal and has no legal action
+        frozen = dict(children=[], root_visits=0, flags=F_NO_LEGAL, where="dead root")
+    for call in range(calls):
+        for _ in range(sims):
+            if frozen is not None:
+                break
+            fl, where = 0, "step"
+            try:
+                node = m.select_leaf()
+                where = "playout"
+                m.backpropagate(node, m.rollout(node.state))
+            except Freeze as e:
+                fl = e.flags
+            except (IndexError, AttributeError) as e:
+                if isinstance(e, AttributeError) and not _raised_no_child(e):
+                    raise
+                fl = F_NO_LEGAL
+            if fl:
+                root = m._root
+                frozen = dict(children=[(a, ch.visits, ch.reward) for a, ch in root.children.items()],
+                              root_visits=root.visits, flags=fl, where=where)
+        if frozen is not None:
+            out.append(frozen)
+            continue
+        root = m._root
+        res = dict(children=[(a, ch.visits, ch.reward) for a, ch in root.children.items()], root_visits=root.visits, flags=0)
+        res["action"], res["value"], res["policies"] = m.finish()
+        a = res["action"] if pick is None else pick(call, res)
+        m._root = root.children[a]
+        m._root.parent = None
+        res["next"] = (m._root.state.n_actions, m._root.state.reward)
+        res["next_board"] = np.array(m._root.state.array, np.int32)
+        out.append(res)
+    _cache[key] = (out, seeds)
+    return _cache[key]
+
+
+def assert_game(res, g, want, tag=""):
+    """A frozen game: the root's children, its visits and the exact flag word (its value is the root's
+    state reward and no part of the contract). Any other game: assert_result."""
+    if not want["flags"]:
+        return assert_result(res, g, want, tag)
+    k = len(want["children"])
+    assert res["flags"][g] == want["flags"], (tag, g, hex(int(res["flags"][g])), hex(want["flags"]))
+    assert res["root_visits"][g] == want["root_visits"], (tag, g)
+    assert res["n_children"][g] == k, (tag, g)
+    got = [(int(res["child_action"][g][j]), int(res["child_visits"][g][j]), int(res["child_reward"][g][j]))
+           for j in range(k)]
+    assert got == [(int(a), int(v), int(r)) for a, v, r in want["children"]], (tag, g)
+
+
+def case(shape, roots, sims, calls, pick=None):
+    """A lockstep batch and its expected side. roots: dict(board (None: the reset board), seed,
+    n_actions, reward); every game's generator is random.Random(9000 + seed), as in the other device
+    tests. Adds want [game][call], seeds [game][call][sim] and states (the roots over the capped oracle)."""
+    want, seeds = [], []
+    for r in roots:
+        w, s = general_search(shape, r["board"], r["seed"], r["n_actions"], r["reward"], sims, 9000 + r["seed"], calls, pick)
+        want.append(w)
+        seeds.append(s)
+    return dict(shape=shape, roots=roots, sims=sims, calls=calls, pick=pick, want=want, seeds=seeds,
+                states=[state(shape, r["board"], r["seed"], r["n_actions"], r["reward"]) for r in roots])
+
+
+def reset_roots(seeds, n_actions):
+    return [dict(board=None, seed=int(s), n_actions=n_actions, reward=0) for s in seeds]
+
+
+def round_seeds(cs, call, games=None):
+    """[sims][games] of one call: the layout of m3_search_run's rollout_seeds."""
+    games = range(len(cs["roots"])) if games is None else games
+    return [[cs["seeds"][g][call][k] for g in games] for k in range(cs["sims"])]
+
+
+def freeze_case():
+    """5x5x6, seeds 1..64, 6 moves, 12 simulations, two calls: of 64 games 2 have a dead root, 2 freeze
+    in an expansion's step and 8 in a playout (counted by the tests, from `want` alone)."""
+    return case((5, 5, 6), reset_roots(range(1, 65), 6), 12, 2)
+
+
+def freeze_kinds(cs):
+    """(dead roots, games frozen in an expansion's step, in a playout, never frozen) as lists of games,
+    by where the reference's exception came from."""
+    kinds = {"dead root": [], "step": [], "playout": [], None: []}
+    for g, w in enumerate(cs["want"]):
+        fz = next((c for c in w if c["flags"]), None)
+        kinds[fz["where"] if fz else None].append(g)
+    return kinds["dead root"], kinds["step"], kinds["playout"], kinds[None]
+
+
+def hetero_case():
+    """9x9x6, 40 mid-episode roots (specials on the boards, n_actions 20..1 twice), rewards
+    seed * 3 % 997, games 36 and 37 terminal at the start; 10 simulations, one call."""
+    from lookahead_ref import mid_episode_states
+    ms = mid_episode_states((9, 9, 6), 40)
+    na = ms["n_actions"].copy()
+    na[36] = na[37] = 0
+    roots = [dict(board=ms["boards"][i], seed=int(ms["seeds"][i]), n_actions=int(na[i]), reward=int(ms["seeds"][i]) * 3 % 997)
+             for i in range(40)]
+    return case((9, 9, 6), roots, 10, 1)
+
+
+def least_visited_last(call, res):
+    """The last of the root's least-visited children."""
+    lo = min(v for _, v, _ in res["children"])
+    return [a for a, v, _ in res["children"] if v == lo][-1]
+
+
+def advance_case():
+    """9x9x6, seeds 401..420, 6 moves, 16 simulations, three calls, each re-rooted at the last of the
+    root's least-visited children."""
+    return case((9, 9, 6), reset_roots(range(401, 421), 6), 16, 3, least_visited_last)
 
 
 # 32 roots the golden file does not cover (its seeds: 3, 11, 29, 101): 9x9x6, every pairing of

@@ -186,3 +186,28 @@ def test_cycling_dead_boards_stop_at_the_cap(golden):
         assert (out == g["next_9x9x6"].reshape(len(s), -1)).all()
         assert (rew == g["reward_9x9x6"]).all() and (drw == g["draws_9x9x6"]).all()
         assert ((flg & 0x17) == 0x14).all() and (nxt == -1).all() and not legal.any()
+
+
+def test_first_scan_takes_table_against_the_host_build():
+    """crafted.first_scan_takes_table (a restatement of get_matches' way past the table) on painted
+    16x16x8 boards under every one of their own legal swaps: where the first scan goes through the table
+    with more groups than it holds, the host build of the step (a 4-group table, KS::GCAP there) leaves
+    for the exact pass; and some swaps do break the plus, so that the group count alone says nothing."""
+    shape = (16, 16, 8)
+    o, hc = Oracle(*shape), HostCore(*shape)
+    assert crafted.lcap(shape) == 4
+    dec = crafted.decode_table(o)
+    rw = crafted.rows(shape, n=64)
+    idx = np.flatnonzero(rw["layout"] != crafted.PLAIN)[:8]
+    through, past = 0, 0
+    for i in idx:
+        assert crafted.first_scan_takes_table(o, rw["boards"][i], int(rw["actions"][i]), dec)  # the painted swap
+        for a in o.legal_actions(rw["boards"][i].astype(np.int32)):
+            many = crafted.first_scan_groups(o, rw["boards"][i], a, dec) > 4
+            if many and crafted.first_scan_takes_table(o, rw["boards"][i], a, dec):
+                hc.apply(rw["boards"][i:i + 1], rw["seeds"][i:i + 1], 3, [a], small=4)
+                assert hc.recomputed == 1, (i, a)
+                through += 1
+            past += many and not crafted.first_scan_takes_table(o, rw["boards"][i], a, dec)
+    assert through >= 50 and past >= 1
+    assert not crafted.first_scan_takes_table(o, o.init_board(5)[0])  # a reset board: no match at all

@@ -71,7 +71,7 @@ def test_golden_searches(golden):
 
 
 def test_130_games_three_calls():
-    """Two full waves and a ragged third, re-rooted twice."""
+    """Eight workgroups of 16 games and a ragged ninth of 2, re-rooted twice."""
     check_against_python((9, 9, 6), range(1, 131), 4, 20, 3)
 
 
@@ -200,3 +200,286 @@ def test_rows_below_columns_is_refused():
     ctx = _native.context(5, 7, 4)
     h = ctypes.c_void_p()
     assert _native.lib().m3_search_create(ctx.handle, 4, 16, ctypes.byref(h)) == -1
+
+
+# ---- frozen games, the exact pass inside a round, roots that are no reset boards -----------------
+# Expected side: search_ref.general_search, the reference's search over the oracle from any root,
+# freezing where include/m3.h says a game freezes.
+RESULT_KEYS = ("best_action", "value", "root_visits", "n_children", "child_action", "child_visits", "child_reward", "flags")
+
+
+def device_roots(cs, games=None):
+    """BoardV2 roots of a search_ref case: its boards, cfg seeds, n_actions and rewards."""
+    R, C, T = cs["shape"]
+    out = []
+    for g in range(len(cs["roots"])) if games is None else games:
+        r, st = cs["roots"][g], cs["states"][g]
+        b = BoardV2(r["n_actions"], BoardConfig(rows=R, columns=C, types=T, seed=r["seed"]), np.asarray(st.array).astype(np.int64))
+        b._reward = r["reward"]
+        out.append(b)
+    return out
+
+
+def device_search(cs, games=None, rngs=None):
+    """One DeviceSearch over the games of a case, at exactly the capacity its calls need."""
+    return DeviceSearch(device_roots(cs, games), cs["sims"], rngs=rngs, node_capacity=2 + cs["calls"] * cs["sims"])
+
+
+def run_call(ds, cs, call, games=None):
+    games = list(range(len(cs["roots"])) if games is None else games)
+    ds.run(ref.round_seeds(cs, call, games))
+    res = ds.result()
+    for j, g in enumerate(games):
+        ref.assert_game(res, j, cs["want"][g][call], (cs["shape"], call, g))
+    return res
+
+
+def test_frozen_games_freeze_alone():
+    """5x5x6, 64 games: 2 dead roots, 2 games frozen by a cap in an expansion's step and 8 in a playout
+    (flag words 0x8, 0x4, and 0x4 / 0xc), 52 never. Every game on both calls; a game frozen in call 0
+    reports the same arrays after call 1."""
+    cs = ref.freeze_case()
+    dead, step, playout, live = ref.freeze_kinds(cs)
+    print(f"freeze case: {len(dead)} dead roots, {len(step)} frozen in a step, {len(playout)} in a playout, "
+          f"{len(live)} never; flag words {sorted({hex(w[-1]['flags']) for w in cs['want'] if w[-1]['flags']})}")
+    assert len(dead) >= 1 and len(step) >= 1 and len(playout) >= 1 and len(live) >= 40
+    n = len(cs["roots"])
+    ds = device_search(cs)
+    for call in range(2):
+        res = run_call(ds, cs, call)
+        if call == 0:
+            first = {k: res[k].copy() for k in RESULT_KEYS}
+        else:
+            for g in (g for g in range(n) if cs["want"][g][0]["flags"]):
+                k = first["n_children"][g]
+                for key in RESULT_KEYS:  # (child arrays: the root's n_children entries)
+                    a, b = (x[key][g][:k] if x[key].ndim == 2 else x[key][g] for x in (first, res))
+                    assert np.array_equal(a, b), (g, key)
+        states = ds.advance(None)  # (a frozen game keeps its root: no bad action)
+        for g, st in enumerate(states):
+            assert st.n_actions == 6 - sum(not w["flags"] for w in cs["want"][g][:call + 1]), (g, call)
+    assert ds.stats()["rounds"] == 24
+    ds.close()
+
+
+def test_call_maps_frozen_games_to_exceptions():
+    """DeviceSearch.__call__: ValueError with a dead root in the batch, RuntimeError with a game frozen
+    by a cap alone, the reference's tuples otherwise."""
+    cs = ref.freeze_case()
+    dead, _, _, live = ref.freeze_kinds(cs)
+    capped = [g for g, w in enumerate(cs["want"]) if w[0]["flags"] == ref.F_SHUFFLE_CAP]
+    both = [g for g, w in enumerate(cs["want"]) if w[0]["flags"] == ref.F_SHUFFLE_CAP | ref.F_NO_LEGAL]
+    assert dead and capped and both and len(live) >= 5  # (both: a playout that went on past its cap)
+
+    def rngs(games):
+        return [random.Random(9000 + cs["roots"][g]["seed"]) for g in games]
+
+    for games, error in ((live[:3] + dead[:1] + live[3:5], ValueError), (live[:3] + capped[:1] + live[3:5], RuntimeError),
+                         (both[:1] + live[:3], RuntimeError)):
+        ds = device_search(cs, games, rngs(games))
+        with pytest.raises(error):
+            ds()
+        ds.close()
+    games = live[:5]
+    ds = device_search(cs, games, rngs(games))
+    for call in range(2):
+        assert ds() == [(cs["want"][g][call]["action"], cs["want"][g][call]["value"], cs["want"][g][call]["policies"])
+                        for g in games], call
+    ds.close()
+
+
+@pytest.mark.parametrize("shape", [(9, 9, 6), (16, 16, 8)], ids=lambda s: "x".join(map(str, s)))
+def test_exact_pass_inside_a_round(shape):
+    """Roots painted with more match groups than the table holds: the expansions of their children
+    leave k_apply for the exact pass, whose count k_search_attach adds up from a word k_search_select
+    zeroes in front of every apply launch.
+
+    Lower bound of apply_exact: the root children whose first scan has more groups than the table
+    holds and goes through the table at all. The group count alone is no bound: get_matches fills the
+    table only with a crossing cell or a run of six on the board, and a root's own legal swaps can take
+    a cell out of the painted plus (9x9x6: 454 children with more than 6 groups, apply_exact 437)."""
+    import crafted
+    rw = crafted.rows(shape, n=64)
+    idx = np.flatnonzero(rw["layout"] != crafted.PLAIN)[:40]
+    assert len(idx) == 40
+    roots = [dict(board=rw["boards"][i], seed=int(rw["seeds"][i]), n_actions=3, reward=0) for i in idx]
+    cs = ref.case(shape, roots, 12, 1)
+    ds = device_search(cs)
+    res = run_call(ds, cs, 0)
+    o, dec = ref.capped_oracle(shape), crafted.decode_table(ref.capped_oracle(shape))
+    kids = [(rw["boards"][i], int(res["child_action"][g][j])) for g, i in enumerate(idx) for j in range(res["n_children"][g])]
+    groups = sum(crafted.first_scan_groups(o, b, a, dec) > crafted.lcap(shape) for b, a in kids)
+    over = sum(crafted.first_scan_groups(o, b, a, dec) > crafted.lcap(shape) and crafted.first_scan_takes_table(o, b, a, dec)
+               for b, a in kids)
+    st = ds.stats()
+    print(f"{shape}: apply_exact {st['apply_exact']} (root children: {len(kids)}, with a first scan of more groups than "
+          f"the table holds: {groups}, of those through the table: {over}), rollout_exact {st['rollout_exact']}")
+    assert over > 0
+    assert over <= st["apply_exact"] <= 40 * 13  # (one expansion per game and round, and the constructor's)
+    assert st["rounds"] == 12
+    ds.close()
+
+
+def test_heterogeneous_roots():
+    """Mid-episode roots with specials, n_actions 20..1 in one batch, non-zero root rewards, and two
+    roots that are terminal when they are set: those keep no child (include/m3.h, m3_search_set_roots)."""
+    cs = ref.hetero_case()
+    ds = device_search(cs)
+    res = run_call(ds, cs, 0)
+    for g in (36, 37):
+        assert (res["best_action"][g], res["n_children"][g], res["root_visits"][g], res["flags"][g]) == (-1, 0, 10, 0)
+        assert res["value"][g] == cs["roots"][g]["reward"] > 0
+    with pytest.raises(ValueError):  # __call__ refuses a terminal root
+        ds()
+    ds.close()
+
+
+def test_advance_with_explicit_actions():
+    """Three calls, each re-rooted at the last of the least-visited root children instead of the best."""
+    cs = ref.advance_case()
+    n = len(cs["roots"])
+    o = ref.capped_oracle(cs["shape"])
+    ds = device_search(cs)
+    for call in range(3):
+        run_call(ds, cs, call)
+        want = [cs["want"][g][call] for g in range(n)]
+        actions = [ref.least_visited_last(call, w) for w in want]
+        assert any(a != w["action"] for a, w in zip(actions, want))
+        states = ds.advance(actions)
+        for g, st in enumerate(states):
+            assert (st.n_actions, st.reward) == want[g]["next"], (call, g)
+            assert np.array_equal(st.array, want[g]["next_board"]), (call, g)
+            assert list(st._actions) == o.legal_actions(want[g]["next_board"]), (call, g)
+    ds.close()
+
+
+def raw_roots(cs):
+    n = len(cs["roots"])
+    boards = np.ascontiguousarray(np.stack([np.asarray(s.array).reshape(-1) for s in cs["states"]]), dtype=np.int8)
+    return (boards, np.array([r["seed"] for r in cs["roots"]], np.uint32), np.array([r["n_actions"] for r in cs["roots"]], np.int32),
+            np.array([r["reward"] for r in cs["roots"]], np.int32)), n
+
+
+def raw_result(h, n, A, null=None):
+    """m3_search_result into sentinel-filled buffers, output `null` (an index into RESULT_KEYS) absent."""
+    out = dict(best_action=np.full(n, -77, np.int32), value=np.full(n, -77, np.int32), root_visits=np.full(n, -77, np.int32),
+               n_children=np.full(n, -77, np.int32), child_action=np.full((n, A), -77, np.int32),
+               child_visits=np.full((n, A), -77, np.int32), child_reward=np.full((n, A), -77, np.int64),
+               flags=np.full(n, 0xABCD, np.uint32))
+    _native.check(_native.lib().m3_search_result(h, *[None if j == null else _native.ptr(out[k])
+                                                    for j, k in enumerate(RESULT_KEYS)]))
+    return out
+
+
+def untouched(a):
+    """Every element still the sentinel raw_result and the advance buffers are filled with."""
+    return bool((a == (0xABCD if a.dtype == np.uint32 else -77)).all())
+
+
+def test_second_set_roots_drops_the_trees():
+    """One m3_search, 64 games of 5x5x6 at capacity 2 + 12: a search that freezes some games, then
+    m3_search_set_roots with other roots and a second search of 12 rounds, which fits only because the
+    slots were given back; flags, statistics and the round count start again."""
+    import ctypes
+    first = ref.freeze_case()
+    second = ref.case((5, 5, 6), ref.reset_roots(range(101, 165), 6), 12, 1)
+    thawed = [g for g in range(64) if first["want"][g][0]["flags"] and not second["want"][g][0]["flags"]]
+    assert thawed
+    ctx, L = _native.context(5, 5, 6), _native.lib()
+    h = ctypes.c_void_p()
+    _native.check(L.m3_search_create(ctx.handle, 64, 2 + 12, ctypes.byref(h)))
+    stats = np.zeros(4, np.uint64)
+    for cs in (first, second):
+        args, n = raw_roots(cs)
+        _native.check(L.m3_search_set_roots(h, *[_native.ptr(a) for a in args]))
+        seeds = np.ascontiguousarray(ref.round_seeds(cs, 0), dtype=np.uint32)
+        _native.check(L.m3_search_run(h, 12, _native.ptr(seeds)))
+        res = raw_result(h, n, ctx.A)
+        for g in range(n):
+            ref.assert_game(res, g, cs["want"][g][0], ("set_roots", cs["roots"][0]["seed"]))
+        _native.check(L.m3_search_stats(h, _native.ptr(stats)))
+        assert stats[1] == 12
+        assert L.m3_search_run(h, 1, _native.ptr(seeds)) == -7  # the object is full again
+    L.m3_search_destroy(h)
+
+
+@pytest.mark.parametrize("shape,cuts", [((10, 8, 9), (0, 1, 16, 33)), ((12, 12, 7), (0, 16, 17))],
+                         ids=["10x8x9-1+15+17", "12x12x7-16+1"])
+def test_batch_composition_does_not_matter(shape, cuts):
+    """A game's result does not depend on the games beside it or on its place in a workgroup of 16:
+    the batch as a whole, and cut into separate searches of one game, a partial and a ragged group."""
+    o = ref.capped_oracle(shape)
+    seeds = [s for s in range(1, 80) if o.legal_actions(o.init_board(s)[0])][:cuts[-1]]
+    assert len(seeds) == cuts[-1]
+    cs = ref.case(shape, ref.reset_roots(seeds, 4), 10, 1)
+    ds = device_search(cs)
+    whole = run_call(ds, cs, 0)
+    ds.close()
+    for lo, hi in zip(cuts, cuts[1:]):
+        games = list(range(lo, hi))
+        ds = device_search(cs, games)
+        part = run_call(ds, cs, 0, games)
+        ds.close()
+        for j, g in enumerate(games):
+            k = whole["n_children"][g]
+            for key in RESULT_KEYS:
+                a, b = (x[key][i][:k] if x[key].ndim == 2 else x[key][i] for x, i in ((whole, g), (part, j)))
+                assert np.array_equal(a, b), (g, key)
+
+
+def test_wide_frame_20x20x6():
+    """The 32 x 32 frame (a side above 16) under the tree kernels: 3 games against the reference."""
+    cs = ref.case((20, 20, 6), ref.reset_roots([1, 2, 3], 2), 6, 1)
+    ds = device_search(cs)
+    run_call(ds, cs, 0)
+    assert ds.stats()["rounds"] == 6
+    ds.close()
+
+
+def test_nullable_outputs():
+    """m3_search_result with each of its eight outputs absent in turn, m3_search_advance on explicit
+    actions with each of its four: what is present equals the call with everything present."""
+    cs = ref.advance_case()
+    n = len(cs["roots"])
+    ctx = _native.context(*cs["shape"])
+    actions = np.array([ref.least_visited_last(0, cs["want"][g][0]) for g in range(n)], np.int32)
+    names = ("boards", "rewards", "n_actions", "legal")
+
+    def advance(null):
+        ds = device_search(cs)
+        ds.run(ref.round_seeds(cs, 0))
+        if null is None:
+            full = raw_result(ds._h, n, ctx.A)
+            for g in range(n):
+                ref.assert_game(full, g, cs["want"][g][0], "nullable")
+            for j in range(8):
+                got = raw_result(ds._h, n, ctx.A, null=j)
+                for i, k in enumerate(RESULT_KEYS):
+                    if i == j:
+                        assert untouched(got[k]), (j, k)
+                    elif got[k].ndim == 2:  # (child arrays: the root's n_children entries are the contract)
+                        assert all(np.array_equal(got[k][g][:c], full[k][g][:c]) for g, c in enumerate(full["n_children"])), (j, k)
+                    else:
+                        assert np.array_equal(got[k], full[k]), (j, k)
+        out = dict(boards=np.full((n, ctx.N), -77, np.int8), rewards=np.full(n, -77, np.int32),
+                   n_actions=np.full(n, -77, np.int32), legal=np.full((n, ctx.words), 0xABCD, np.uint32))
+        _native.check(_native.lib().m3_search_advance(ds._h, _native.ptr(actions),
+                                                      *[None if k == null else _native.ptr(out[k]) for k in names]))
+        ds.run(ref.round_seeds(cs, 1))  # the search goes on from the new roots, whatever was asked for
+        res = ds.result()
+        for g in range(n):
+            ref.assert_game(res, g, cs["want"][g][1], ("nullable", null))
+        ds.close()
+        return out
+
+    full = advance(None)
+    o = ref.capped_oracle(cs["shape"])
+    for g in range(n):
+        w = cs["want"][g][0]
+        assert (full["n_actions"][g], full["rewards"][g]) == w["next"]
+        assert np.array_equal(full["boards"][g], w["next_board"].reshape(-1))
+        assert _native.bits_to_actions(full["legal"][g], ctx.A) == o.legal_actions(w["next_board"])
+    for null in names:
+        got = advance(null)
+        for k in names:
+            assert untouched(got[k]) if k == null else np.array_equal(got[k], full[k]), (null, k)

@@ -5,6 +5,11 @@ the result, the re-rooting -- for the host; the step and the playout between the
 oracle. Expected side: ``match3tile.mcts.MCTS`` over the same oracle (search_ref.py), which
 tests/test_mcts_cpu.py holds to the real reference's outputs, and those outputs themselves
 (tests/golden/mcts.npz, the se_* cases).
+
+The cases of search_ref.general_search -- games that freeze beside games that go on, roots that are no
+reset boards (two of them terminal from the start), re-rooting at a chosen child, a second set of
+roots on a live object -- run here first and on the device in tests/test_gpu_search.py. The driver
+hands the core the step flags k_apply would (search_host.py, _round): M3_FLAG_NO_LEGAL beside a cap.
 """
 import math
 import os
@@ -95,6 +100,96 @@ def test_terminal_root_and_order_of_calls():
     L.sh_destroy(h)
 
 
+RESULT_KEYS = ("best_action", "value", "root_visits", "n_children", "child_action", "child_visits", "child_reward", "flags")
+
+
+def run_case(cs, record=None):
+    """A case of search_ref as one lockstep HostSearch at exactly the capacity its calls need; yields
+    (call, result arrays, HostSearch). The caller re-roots."""
+    hs = sh.HostSearch(ref.capped_oracle(cs["shape"]), cs["states"], 2 + cs["calls"] * cs["sims"], record)
+    for call in range(cs["calls"]):
+        assert hs.run(cs["sims"], ref.round_seeds(cs, call)) == 0
+        yield call, hs.result(), hs
+
+
+def check_freeze_counts(cs):
+    dead, step, playout, live = ref.freeze_kinds(cs)
+    print(f"freeze case: {len(dead)} dead roots, {len(step)} frozen in a step, {len(playout)} in a playout, "
+          f"{len(live)} never; flag words {sorted({hex(w[-1]['flags']) for w in cs['want'] if w[-1]['flags']})}")
+    assert len(dead) >= 1 and len(step) >= 1 and len(playout) >= 1 and len(live) >= 40
+    return dead, step, playout, live
+
+
+def test_frozen_games_freeze_alone():
+    """5x5x6, 64 games in lockstep: dead roots, caps in an expansion's step and in a playout. A frozen
+    game reports its tree as it stood and its flag word; the games beside it go on as if alone."""
+    cs = ref.freeze_case()
+    check_freeze_counts(cs)
+    n = len(cs["roots"])
+    for call, res, hs in run_case(cs):
+        for g in range(n):
+            ref.assert_game(res, g, cs["want"][g][call], ("freeze", call))
+        if call == 0:
+            first = {k: res[k].copy() for k in RESULT_KEYS}
+        else:
+            for g in (g for g in range(n) if cs["want"][g][0]["flags"]):
+                for k in RESULT_KEYS:
+                    assert np.array_equal(res[k][g], first[k][g]), (g, k)
+        bad, _, _, na = hs.advance(res["best_action"])  # (a frozen game keeps its root: not a bad action)
+        assert bad == 0
+        for g in range(n):
+            assert na[g] == 6 - sum(not w["flags"] for w in cs["want"][g][:call + 1]), (g, call)  # one move per unfrozen call
+
+
+def test_heterogeneous_roots():
+    """Mid-episode roots with specials, 20 different n_actions in one batch, non-zero root rewards, and
+    two roots that are terminal when they are set: those keep no child (include/m3.h,
+    m3_search_set_roots -- the reference's constructor would attach the state to itself)."""
+    cs = ref.hetero_case()
+    assert sorted({r["n_actions"] for r in cs["roots"]}) == list(range(0, 21))
+    (_, res, hs), = run_case(cs)
+    for g in range(40):
+        ref.assert_game(res, g, cs["want"][g][0], "hetero")
+    for g in (36, 37):
+        assert cs["roots"][g]["reward"] > 0
+        assert (res["best_action"][g], res["n_children"][g], res["root_visits"][g], res["flags"][g]) == (-1, 0, 10, 0)
+        assert res["value"][g] == cs["roots"][g]["reward"]
+        assert hs.nodes_used(g) == 1
+
+
+def test_advance_with_explicit_actions():
+    """Three calls, each re-rooted at the last of the least-visited root children instead of the best."""
+    cs = ref.advance_case()
+    n = len(cs["roots"])
+    for call, res, hs in run_case(cs):
+        for g in range(n):
+            ref.assert_game(res, g, cs["want"][g][call], ("advance", call))
+        actions = [ref.least_visited_last(call, cs["want"][g][call]) for g in range(n)]
+        first = [cs["want"][g][call]["children"][0][0] for g in range(n)]
+        assert any(a != cs["want"][g][call]["action"] for g, a in enumerate(actions))  # not the default re-rooting
+        assert any(a != f for a, f in zip(actions, first))                             # nor the first child
+        bad, _, rew, na = hs.advance(actions)
+        assert bad == 0
+        assert [(int(a), int(b)) for a, b in zip(na, rew)] == [cs["want"][g][call]["next"] for g in range(n)], call
+
+
+def test_second_set_roots_drops_the_trees():
+    """One object at capacity 2 + 12: a search that freezes some games, then other roots and a second
+    search of 12 rounds, which fits only because the slots were given back; the flag words start again."""
+    first = ref.freeze_case()
+    second = ref.case((5, 5, 6), ref.reset_roots(range(101, 165), 6), 12, 1)
+    assert [g for g in range(64) if first["want"][g][0]["flags"] and not second["want"][g][0]["flags"]]
+    hs = sh.HostSearch(ref.capped_oracle((5, 5, 6)), first["states"], 2 + 12)
+    for cs in (first, second):
+        if cs is second:
+            hs.set_roots(cs["states"])
+        assert hs.run(12, ref.round_seeds(cs, 0)) == 0
+        res = hs.result()
+        for g in range(64):
+            ref.assert_game(res, g, cs["want"][g][0], ("set_roots", cs["roots"][0]["seed"]))
+        assert hs.run(1, [[1] * 64]) == -7  # the object is full again
+
+
 def test_log_table_is_libm_log():
     """m3_search_log_table (host only) and the core's table: math.log, compared as bits."""
     want = np.array([math.log(v) for v in range(1, 65537)])
@@ -140,3 +235,24 @@ def test_search_core_under_asan_ubsan(tmp_path):
     out = r.stdout.strip().splitlines()
     assert out[:-1] == lines
     assert f"3 results, 1 refused, {2 + 3 * 7} of {2 + 3 * 7} nodes" in out[-1]
+
+
+def test_freeze_scenario_under_asan_ubsan(tmp_path):
+    """The 64 games of test_frozen_games_freeze_alone (both calls at exactly node_capacity, frozen games
+    among them) replayed by the stand-alone program: it must print the Python run's results."""
+    cs = ref.freeze_case()
+    rec, lines, used = [], [], 0
+    for call, res, hs in run_case(cs, record=rec):
+        lines += sh.result_lines(res)
+        assert hs.advance(res["best_action"])[0] == 0
+        used = max(hs.nodes_used(g) for g in range(len(cs["roots"])))
+    assert any(line.split()[5] != "0" for line in lines)  # (flags: frozen games are in the text)
+    path = tmp_path / "scenario.txt"
+    path.write_text(" ".join(map(str, rec)) + "\n")
+    d = os.path.join(ROOT, "tests", "search_host")
+    subprocess.run(["make", "-C", d, "asan"], check=True, capture_output=True)
+    r = subprocess.run([os.path.join(d, "build", "search_asan"), str(path)], capture_output=True, text=True)
+    assert r.returncode == 0 and "checks ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+    out = r.stdout.strip().splitlines()
+    assert out[:-1] == lines
+    assert f"2 results, 0 refused, {used} of {2 + 2 * 12} nodes" in out[-1]
