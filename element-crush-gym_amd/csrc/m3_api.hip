@@ -729,6 +729,14 @@ int m3_env_set_shards(m3_env* e, int nshards) {
     int rc = sync_env(e);
     if (rc) return rc;
     destroy_shards(e);
+    // Shard slot s keeps its counter blocks across the call, and only its own k_env_fix rotates them
+    // (CBLOCKS): a slot that sat out some steps comes back with the blocks of its last steps still
+    // counting their overflow lists, continuation records and prefetch queues. Nothing is in flight
+    // and every list of a past step is consumed, so all blocks of all slots start the next step empty;
+    // the stats words behind them stay.
+    for (int s = 0; s < MAX_SHARDS; ++s)
+        HIP_TRY(hipMemsetAsync(e->counters + 64 * s, 0, 8 * CBLOCKS * 4, e->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(e->ctx->stream));
     // shard boundaries on 256-board multiples
     const int64_t per = ((e->n + nshards - 1) / nshards + BLOCK - 1) / BLOCK * BLOCK;
     for (int s = 0; s < nshards; ++s) {
@@ -1133,7 +1141,7 @@ int m3_env_stats(m3_env* e, uint64_t out[4]) {
     std::vector<uint32_t> h(64 * MAX_SHARDS);
     HIP_TRY(hipMemcpy(h.data(), e->counters, h.size() * 4, hipMemcpyDeviceToHost));
     out[0] = out[1] = out[2] = out[3] = 0;
-    for (size_t s = 0; s < e->shards.size(); ++s) {
+    for (size_t s = 0; s < (size_t)MAX_SHARDS; ++s) {  // every slot: one not in use now may have counted earlier
         out[0] += h[64 * s + 40];  // steps recomputed (cache exhausted or > table groups)
         out[1] += h[64 * s + 42];  // resets recomputed by the wave-cooperative pass (see include/m3.h)
         out[2] += h[64 * s + 41];  // autoresets (episodes prefetched)

@@ -2211,7 +2211,11 @@ int fill_next_slots(m3_env* e) {
 template <class CF>
 int rederive(m3_env* e) {
     m3_ctx* c = e->ctx;
-    HIP_TRY(hipMemsetAsync(e->counters, 0, 64 * 4 * MAX_SHARDS, c->stream));
+    // (the stats words 40..42 of every shard slot stay: they count since the last m3_env_reset)
+    for (int s = 0; s < MAX_SHARDS; ++s) {
+        HIP_TRY(hipMemsetAsync(e->counters + 64 * s, 0, 40 * 4, c->stream));
+        HIP_TRY(hipMemsetAsync(e->counters + 64 * s + 43, 0, (64 - 43) * 4, c->stream));
+    }
     HIP_TRY(hipMemsetAsync(e->slot, 0, e->n, c->stream));
     const int64_t g = std::min<int64_t>((e->n + 255) / 256, 4096);
     hipLaunchKernelGGL(k_mt397, dim3((unsigned)g), dim3(256), 0, c->stream, e->n, e->seeds, e->m397);

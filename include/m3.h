@@ -236,7 +236,10 @@ int m3_env_reset(m3_env *env, const uint32_t *seeds, uint32_t seed_base);
 
 /* Split the boards into nshards (1..8) contiguous shards, each stepped on its
  * own HIP stream (plus one prefetch stream per shard for the autoreset
- * launches). Results do not depend on it. Default: 1. Each shard adds two
+ * launches). Results do not depend on it, and it may be called between any
+ * two steps: the call waits for the env's work, the run goes on exactly as it
+ * would have, and the m3_env_stats counters stay cumulative across it (a shard
+ * that is no longer in use keeps what it counted). Default: 1. Each shard adds two
  * streams; with GPU_MAX_HW_QUEUES >= 8 in the process, 2 shards are fastest
  * (the shards' step kernels fill each other's tails); with HIP's default 4
  * queues, 1. */
@@ -325,7 +328,8 @@ int m3_env_gather_device(m3_env *env, int32_t *d_out);
  * stream the gathers run on), to hold a gather in flight while later steps run. */
 int m3_env_debug_stall(m3_env *env, uint32_t usec);
 
-/* Cumulative counters since the last m3_env_reset: out[0] steps recomputed on
+/* Cumulative counters since the last m3_env_reset (m3_env_set_shards, m3_env_set_autoreset and
+ * m3_env_set leave them counting): out[0] steps recomputed on
  * the exact fallback pass (>= 624 MT draws or more match groups than the LDS
  * table), out[1] resets recomputed by the wave-cooperative pass (9x9x6: a
  * reset of more than 624 MT draws -- exactly 624 still fits the register chain
