@@ -1,6 +1,7 @@
 // m3_api.hip -- the C ABI of include/m3.h (kernels and launchers: m3_kernels.hpp).
 #include "m3_kernels.hpp"
 #include "m3_search.hpp"
+#include "m3_search_nn.hpp"
 
 #include <string>
 
@@ -1548,6 +1549,346 @@ int m3_search_ucb1(m3_ctx* c, int64_t n, const int64_t* reward_sum, const int32_
                                     hc.dev<const int32_t>(i_p), hc.dev<const double>(i_c), hc.dev<const double>(i_t),
                                     hc.dev<double>(o)));
     return hc.finish();
+}
+
+}  // extern "C"
+
+// ---- network-guided device MCTS trees (m3_search_nn.hpp: the tree kernels) -------------
+struct m3_search_nn {
+    m3_ctx* ctx = nullptr;
+    int64_t n = 0;
+    int32_t cap = 0;
+    bool ready = false;
+    int phase = 0;         // batches handed out since set_roots: 0 the roots', 1 the construction's expansion, 2 simulations
+    bool pending = false;  // a batch is out and not fed yet
+    int64_t used = 0;      // nodes below the root ever attached, per game at most (m3s::search_run_fits)
+    m3s::NNRound R{};
+    uint32_t* seeds = nullptr;  // [n] cfg.seed of each game
+    int8_t* out_boards = nullptr;
+    int32_t* out_reward = nullptr;
+    uint32_t *out_draws = nullptr, *out_flags = nullptr, *out_legal = nullptr, *apply_list = nullptr;
+    uint32_t* counters = nullptr;  // [0] the apply launch's overflow count
+    int32_t* keep_best = nullptr;  // [n] best_action of the last m3_search_nn_result
+    uint64_t* stats = nullptr;
+    float *lin_values = nullptr, *lin_logits = nullptr;  // the built-in evaluator's answer
+    uint64_t fed_host = 0, fed_device = 0, fed_linear = 0;
+    std::vector<void*> owned;
+};
+
+namespace {
+
+template <class T>
+hipError_t nn_alloc(m3_search_nn* s, T** field, size_t bytes) {
+    hipError_t err = hipMalloc((void**)field, bytes ? bytes : 4);
+    if (err == hipSuccess) s->owned.push_back(*field);
+    return err;
+}
+
+// The launches up to the next evaluation batch (the roots' batch is written by m3_search_nn_set_roots).
+int enqueue_nn_batch(m3_search_nn* s) {
+    if (s->phase == 0) return M3_OK;
+    m3_ctx* c = s->ctx;
+    HIP_TRY(m3s::launch_nn_select(c->stream, s->R));
+    ApplyArgs a{};
+    a.shape = c->sdesc;
+    a.n = s->n;
+    a.boards = s->R.row_boards;
+    a.seeds = s->seeds;
+    a.n_actions = s->R.row_na;
+    a.actions = s->R.T.action;
+    a.out_boards = s->out_boards;
+    a.reward = s->out_reward;
+    a.draws = s->out_draws;
+    a.flags = s->out_flags;
+    a.legal = s->out_legal;
+    a.ovf_count = s->counters;
+    a.ovf_list = s->apply_list;
+    int rc = with_shape(c->shape, [&](auto cf) { return launch_apply<decltype(cf)>(c, a); });
+    if (rc) return rc;
+    HIP_TRY(m3s::launch_nn_attach(c->stream, s->R));
+    return M3_OK;
+}
+
+// the rest of the round once the evaluator's answer is in device memory
+int enqueue_nn_commit(m3_search_nn* s, const float* d_values, const float* d_logits) {
+    const bool sim = s->phase >= 2;
+    HIP_TRY(m3s::launch_nn_commit(s->ctx->stream, s->R, d_values, d_logits, sim ? 1 : 0));
+    if (sim) s->used += 1;
+    else s->phase += 1;
+    s->pending = false;
+    return M3_OK;
+}
+
+int nn_fits(m3_search_nn* s, int32_t simulations) {
+    if (m3s::search_run_fits(s->used, simulations, s->cap)) return M3_OK;
+    return set_err(M3_ERR_CAP, "%d simulations on trees of up to %lld nodes do not fit node_capacity %d", simulations,
+                   (long long)s->used + 1, s->cap);
+}
+
+int nn_state(const m3_search_nn* s, const char* entry, bool want_pending) {
+    if (!s->ready) return set_err(M3_ERR_STATE, "%s before m3_search_nn_set_roots", entry);
+    if (s->pending != want_pending)
+        return set_err(M3_ERR_STATE, want_pending ? "%s without a pending batch (m3_search_nn_batch first)"
+                                                  : "%s while a batch is pending (feed it first)", entry);
+    return M3_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int m3_search_nn_create(m3_ctx* c, int64_t n, int32_t node_capacity, m3_search_nn** out) {
+    CHECK_ARG(c && out && n > 0 && node_capacity >= 2, "bad arguments");
+    CHECK_ARG(n < (int64_t)1 << 31, "n too large");
+    *out = nullptr;
+    int rc = check_ids_on_board(c);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    m3_search_nn* s = new m3_search_nn;
+    s->ctx = c;
+    s->n = n;
+    s->cap = node_capacity;
+    m3s::NTree& T = s->R.T;
+    T.n = n;
+    T.cap = node_capacity;
+    T.N = c->N;
+    T.AW = c->AW;
+    T.A = c->A;
+    const size_t nodes = (size_t)n * (size_t)node_capacity, bytes = (size_t)n * c->N, aw = (size_t)n * 4 * c->AW;
+    hipError_t err = hipSuccess;
+    auto alloc = [&](auto** p, size_t sz) {
+        if (err == hipSuccess) err = nn_alloc(s, p, sz);
+    };
+    alloc(&T.hot, nodes * sizeof(m3s::NNodeHot));
+    alloc(&T.link, nodes * sizeof(m3s::SNodeLink));
+    alloc(&T.untried, nodes * 4 * c->AW);
+    alloc(&T.boards, nodes * c->N);
+    alloc(&T.logits, nodes * 4 * c->A);
+    alloc(&T.root, n * 4);
+    alloc(&T.used, n * 4);
+    alloc(&T.leaf, n * 4);
+    alloc(&T.expanded, n * 4);
+    alloc(&T.action, n * 4);
+    alloc(&T.pending, n * 4);
+    alloc(&T.gflags, n * 4);
+    double* log_tab = nullptr;
+    alloc(&log_tab, ((size_t)node_capacity + 1) * 8);
+    T.log_tab = log_tab;
+    alloc(&s->R.row_boards, bytes);
+    alloc(&s->R.row_na, n * 4);
+    alloc(&s->R.ev_boards, bytes);
+    alloc(&s->R.ev_need, n);
+    alloc(&s->seeds, n * 4);
+    alloc(&s->out_boards, bytes);
+    alloc(&s->out_reward, n * 4);
+    alloc(&s->out_draws, n * 4);
+    alloc(&s->out_flags, n * 4);
+    alloc(&s->out_legal, aw);
+    alloc(&s->apply_list, n * 4);
+    alloc(&s->counters, 32);
+    alloc(&s->keep_best, n * 4);
+    alloc(&s->stats, 32);
+    alloc(&s->lin_values, n * 4);
+    alloc(&s->lin_logits, (size_t)n * 4 * c->A);
+    s->R.out_boards = s->out_boards;
+    s->R.out_reward = s->out_reward;
+    s->R.out_flags = s->out_flags;
+    s->R.out_legal = s->out_legal;
+    s->R.apply_ovf = s->counters;
+    s->R.stats = s->stats;
+    std::vector<double> tab((size_t)node_capacity + 1);
+    m3s::search_log_table(node_capacity, tab.data());  // log on the host only (m3_search_core.hpp)
+    if (err == hipSuccess) err = hipMemcpyAsync(log_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream);
+    if (err == hipSuccess) err = hipMemsetAsync(s->counters, 0, 32, c->stream);
+    if (err == hipSuccess) err = hipMemsetAsync(s->stats, 0, 32, c->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
+    if (err != hipSuccess) {
+        m3_search_nn_destroy(s);
+        return set_err(M3_ERR_HIP, "search_nn allocation (%lld games x %d nodes): %s", (long long)n, node_capacity,
+                       hipGetErrorString(err));
+    }
+    *out = s;
+    return M3_OK;
+}
+
+int m3_search_nn_destroy(m3_search_nn* s) {
+    if (!s) return M3_OK;
+    (void)hipSetDevice(s->ctx->device);
+    (void)hipStreamSynchronize(s->ctx->stream);
+    for (void* p : s->owned) (void)hipFree(p);
+    delete s;
+    return M3_OK;
+}
+
+int m3_search_nn_set_roots(m3_search_nn* s, const int8_t* boards, const uint32_t* seeds, const int32_t* n_actions,
+                           const int32_t* rewards) {
+    CHECK_ARG(s && boards && seeds && n_actions && rewards, "bad arguments");
+    m3_ctx* c = s->ctx;
+    const int64_t n = s->n;
+    for (size_t i = 0, e = (size_t)n * c->N; i < e; ++i)
+        if (boards[i] < 0) return bad_cells_error();
+    HIP_TRY(hipSetDevice(c->device));
+    s->ready = false;
+    HostCall hc(c);
+    const int i_b = hc.input(boards, n * (size_t)c->N), i_s = hc.input(seeds, n * 4ull),
+              i_na = hc.input(n_actions, n * 4ull), i_r = hc.input(rewards, n * 4ull);
+    int rc = hc.begin(false, 16, 0);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(s->seeds, hc.dev<const uint32_t>(i_s), n * 4ull, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(s->stats, 0, 32, c->stream));
+    rc = with_shape(c->shape, [&](auto cf) {
+        return launch_legal<decltype(cf)>(c, n, hc.dev<const int8_t>(i_b), s->out_legal);
+    });
+    if (rc) return rc;
+    HIP_TRY(m3s::launch_nn_init(c->stream, s->R, hc.dev<const int8_t>(i_b), hc.dev<const int32_t>(i_na),
+                                hc.dev<const int32_t>(i_r), s->out_legal));
+    rc = hc.finish();
+    if (rc) return rc;
+    s->used = 1;
+    s->phase = 0;
+    s->pending = false;
+    s->fed_host = s->fed_device = s->fed_linear = 0;
+    s->ready = true;
+    return M3_OK;
+}
+
+int m3_search_nn_batch(m3_search_nn* s, int32_t remaining, const int8_t** d_boards, const uint8_t** d_need) {
+    CHECK_ARG(s && d_boards && d_need, "bad arguments");
+    int rc = nn_state(s, "m3_search_nn_batch", false);
+    if (rc) return rc;
+    if (s->phase >= 2) {
+        CHECK_ARG(remaining >= 1, "remaining < 1 for a simulation round");
+        rc = nn_fits(s, remaining);  // before anything is enqueued
+        if (rc) return rc;
+    }
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    rc = enqueue_nn_batch(s);
+    if (rc) return rc;
+    s->pending = true;
+    *d_boards = s->R.ev_boards;
+    *d_need = s->R.ev_need;
+    return M3_OK;
+}
+
+int m3_search_nn_feed_device(m3_search_nn* s, const float* d_values, const float* d_logits) {
+    CHECK_ARG(s && d_values && d_logits, "bad arguments");
+    int rc = nn_state(s, "m3_search_nn_feed_device", true);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    rc = enqueue_nn_commit(s, d_values, d_logits);
+    if (rc == M3_OK) s->fed_device += 1;
+    return rc;
+}
+
+int m3_search_nn_feed(m3_search_nn* s, const float* values, const float* logits) {
+    CHECK_ARG(s && values && logits, "bad arguments");
+    int rc = nn_state(s, "m3_search_nn_feed", true);
+    if (rc) return rc;
+    m3_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    HostCall hc(c);
+    const int i_v = hc.input(values, (size_t)s->n * 4), i_l = hc.input(logits, (size_t)s->n * c->A * 4);
+    rc = hc.begin(false, 0, 0);
+    if (rc) return rc;
+    rc = enqueue_nn_commit(s, hc.dev<const float>(i_v), hc.dev<const float>(i_l));
+    if (rc) return rc;
+    s->fed_host += 1;
+    return hc.finish();  // the staging is the context's: the kernel has read it when this returns
+}
+
+int m3_search_nn_run_linear(m3_search_nn* s, int32_t simulations, const float* d_W) {
+    CHECK_ARG(s && simulations >= 0 && d_W, "bad arguments");
+    int rc = nn_state(s, "m3_search_nn_run_linear", false);
+    if (rc) return rc;
+    rc = nn_fits(s, simulations);  // before anything is enqueued
+    if (rc) return rc;
+    m3_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const int CH = m3s::nn_onehot_width(c->T);
+    int32_t left = simulations;
+    while (s->phase < 2 || left > 0) {
+        if (s->phase >= 2) --left;
+        rc = enqueue_nn_batch(s);
+        if (rc) return rc;
+        HIP_TRY(m3s::launch_nn_linear(c->stream, s->R, CH, d_W, s->lin_values, s->lin_logits));
+        rc = enqueue_nn_commit(s, s->lin_values, s->lin_logits);
+        if (rc) return rc;
+        s->fed_linear += 1;
+    }
+    return M3_OK;
+}
+
+int m3_search_nn_result(m3_search_nn* s, int32_t* best_action, int32_t* value, int32_t* root_visits, int32_t* n_children,
+                        int32_t* child_action, int32_t* child_visits, float* child_value_sum, float* child_prior,
+                        uint32_t* flags) {
+    CHECK_ARG(s, "null search");
+    int rc = nn_state(s, "m3_search_nn_result", false);
+    if (rc) return rc;
+    m3_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = (size_t)s->n, na = n * c->A;
+    HostCall hc(c);
+    const int o_a = hc.output(best_action, n * 4), o_v = hc.output(value, n * 4), o_rv = hc.output(root_visits, n * 4),
+              o_nc = hc.output(n_children, n * 4), o_ca = hc.output(child_action, na * 4),
+              o_cv = hc.output(child_visits, na * 4), o_cs = hc.output(child_value_sum, na * 4),
+              o_cp = hc.output(child_prior, na * 4), o_f = hc.output(flags, n * 4);
+    rc = hc.begin(false, 16, 0);
+    if (rc) return rc;
+    m3s::NResult r{hc.dev<int32_t>(o_a),  hc.dev<int32_t>(o_v),  hc.dev<int32_t>(o_rv), hc.dev<int32_t>(o_nc),
+                   hc.dev<int32_t>(o_ca), hc.dev<int32_t>(o_cv), hc.dev<float>(o_cs),   hc.dev<float>(o_cp),
+                   hc.dev<uint32_t>(o_f)};
+    HIP_TRY(m3s::launch_nn_finish(c->stream, s->R.T, r, s->keep_best, s->stats));
+    return hc.finish();
+}
+
+int m3_search_nn_advance(m3_search_nn* s, const int32_t* actions, int8_t* out_boards, int32_t* out_rewards,
+                         int32_t* out_n_actions, uint32_t* out_legal_bits) {
+    CHECK_ARG(s, "null search");
+    int rc = nn_state(s, "m3_search_nn_advance", false);
+    if (rc) return rc;
+    m3_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = (size_t)s->n;
+    std::vector<uint32_t> fl(n);
+    HostCall hc(c);
+    const int i_a = actions ? hc.input(actions, n * 4) : -1;
+    const int o_b = hc.output(out_boards, n * c->N), o_r = hc.output(out_rewards, n * 4),
+              o_na = hc.output(out_n_actions, n * 4), o_l = hc.output(out_legal_bits, n * 4 * c->AW),
+              o_f = hc.output(fl.data(), n * 4);
+    rc = hc.begin(false, 16, 0);
+    if (rc) return rc;
+    // (outputs the caller does not want land in the round's row buffers, rewritten by the next round)
+    int8_t* d_b = out_boards ? hc.dev<int8_t>(o_b) : s->R.row_boards;
+    HIP_TRY(m3s::launch_nn_advance(c->stream, s->R.T, actions ? hc.dev<const int32_t>(i_a) : s->keep_best, d_b,
+                                   out_rewards ? hc.dev<int32_t>(o_r) : s->out_reward,
+                                   out_n_actions ? hc.dev<int32_t>(o_na) : s->R.row_na, hc.dev<uint32_t>(o_f)));
+    if (out_legal_bits) {
+        rc = with_shape(c->shape, [&](auto cf) { return launch_legal<decltype(cf)>(c, s->n, d_b, hc.dev<uint32_t>(o_l)); });
+        if (rc) return rc;
+    }
+    rc = hc.finish();
+    if (rc) return rc;
+    int64_t bad = 0;
+    for (uint32_t f : fl) bad += (f & M3_FLAG_BAD_ACTION) != 0;
+    if (bad)
+        return set_err(M3_ERR_INVALID, "%lld of %lld games: the action has no expanded child of the root (their roots "
+                       "stay; the outputs hold the current roots)", (long long)bad, (long long)n);
+    return M3_OK;
+}
+
+int m3_search_nn_stats(m3_search_nn* s, uint64_t out[6]) {
+    CHECK_ARG(s && out, "bad arguments");
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    uint64_t dev[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(dev, s->stats, 32, hipMemcpyDeviceToHost, s->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+    out[0] = dev[0];
+    out[1] = dev[1];
+    out[2] = dev[2];
+    out[3] = s->fed_host;
+    out[4] = s->fed_device;
+    out[5] = s->fed_linear;
+    return M3_OK;
 }
 
 }  // extern "C"

@@ -8,25 +8,6 @@
 namespace m3s {
 namespace {
 
-__device__ __forceinline__ int64_t game0() { return (int64_t)blockIdx.x * SEARCH_GAMES; }
-__device__ __forceinline__ int games_here(int64_t n) {
-    const int64_t left = n - game0();
-    return left < SEARCH_GAMES ? (int)left : SEARCH_GAMES;
-}
-
-// The workgroup's boards, one after the other, the lanes across a board's bytes: dst(j) / src(j)
-// are the addresses of game j's board. The loads of a few boards are in flight together.
-template <class Dst, class Src>
-__device__ __forceinline__ void copy_boards(int nb, int N, Dst dst, Src src) {
-#pragma unroll 4
-    for (int j = 0; j < nb; ++j) {
-        int8_t* d = dst(j);  // nullptr: nothing to copy for this game
-        if (d) search_copy_board(d, src(j), N, threadIdx.x, SEARCH_BLOCK);
-    }
-}
-// kernels without a board to move: one lane per game, every lane of the wave in use
-__device__ __forceinline__ int64_t lane_game() { return (int64_t)blockIdx.x * SEARCH_BLOCK + threadIdx.x; }
-
 __global__ void __launch_bounds__(SEARCH_BLOCK) k_search_init(STree T, const int8_t* boards, const int32_t* n_actions,
                                                               const int32_t* rewards, const uint32_t* legal) {
     const int64_t g0 = game0(), g = g0 + threadIdx.x;
@@ -117,9 +98,6 @@ __global__ void __launch_bounds__(SEARCH_BLOCK) k_search_ucb1(int64_t n, const i
     const int64_t i = lane_game();
     if (i < n) out[i] = search_ucb1(reward_sum[i], visits[i], log_tab[parent_visits[i]], c[i]);
 }
-
-unsigned grid_for(int64_t n) { return (unsigned)((n + SEARCH_GAMES - 1) / SEARCH_GAMES); }
-unsigned grid_flat(int64_t n) { return (unsigned)((n + SEARCH_BLOCK - 1) / SEARCH_BLOCK); }
 
 }  // namespace
 

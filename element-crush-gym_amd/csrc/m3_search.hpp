@@ -36,6 +36,29 @@ constexpr int SEARCH_BLOCK = 64;  // threads per workgroup: one wave
 // 64, and each wave moves 16 boards, not 64, behind its walk (DESIGN.md §6.0.1 has the A/B).
 constexpr int SEARCH_GAMES = 16;
 
+// ---- what the tree kernels of m3_search.hip and m3_search_nn.hip share --------------------------
+__device__ __forceinline__ int64_t game0() { return (int64_t)blockIdx.x * SEARCH_GAMES; }
+__device__ __forceinline__ int games_here(int64_t n) {
+    const int64_t left = n - game0();
+    return left < SEARCH_GAMES ? (int)left : SEARCH_GAMES;
+}
+
+// The workgroup's boards, one after the other, the lanes across a board's bytes: dst(j) / src(j)
+// are the addresses of game j's board. The loads of a few boards are in flight together.
+template <class Dst, class Src>
+__device__ __forceinline__ void copy_boards(int nb, int N, Dst dst, Src src) {
+#pragma unroll 4
+    for (int j = 0; j < nb; ++j) {
+        int8_t* d = dst(j);  // nullptr: nothing to copy for this game
+        if (d) search_copy_board(d, src(j), N, threadIdx.x, SEARCH_BLOCK);
+    }
+}
+// kernels without a board to move: one lane per game, every lane of the wave in use
+__device__ __forceinline__ int64_t lane_game() { return (int64_t)blockIdx.x * SEARCH_BLOCK + threadIdx.x; }
+
+inline unsigned grid_for(int64_t n) { return (unsigned)((n + SEARCH_GAMES - 1) / SEARCH_GAMES); }
+inline unsigned grid_flat(int64_t n) { return (unsigned)((n + SEARCH_BLOCK - 1) / SEARCH_BLOCK); }
+
 hipError_t launch_search_init(hipStream_t st, const STree& T, const int8_t* boards, const int32_t* n_actions,
                               const int32_t* rewards, const uint32_t* legal);
 hipError_t launch_search_select(hipStream_t st, const SearchRound& r);

@@ -26,6 +26,7 @@ FLAG_NO_LEGAL = 0x08
 FLAG_SHUFFLED = 0x10
 FLAG_CASCADE_CAP = 0x100
 FLAG_RESET_CAP = 0x200
+FLAG_BAD_EVAL = 0x400
 
 ENV_BOARDS, ENV_REWARD, ENV_DONE, ENV_TRUNCATED, ENV_SCORE, ENV_MOVES, ENV_FLAGS, ENV_NEXT_ACTION, \
     ENV_LEGAL, ENV_SEEDS, ENV_DRAWS, ENV_GATHERED = range(12)
@@ -44,6 +45,9 @@ EXPORTS = [
     "m3_env_kernel_ms", "m3_env_step_kernel_ms",
     "m3_search_create", "m3_search_destroy", "m3_search_log_table", "m3_search_set_roots", "m3_search_run",
     "m3_search_result", "m3_search_advance", "m3_search_stats", "m3_search_ucb1",
+    "m3_search_nn_create", "m3_search_nn_destroy", "m3_search_nn_set_roots", "m3_search_nn_batch",
+    "m3_search_nn_feed_device", "m3_search_nn_feed", "m3_search_nn_run_linear", "m3_search_nn_result",
+    "m3_search_nn_advance", "m3_search_nn_stats",
 ]
 
 
@@ -123,6 +127,16 @@ def lib():
             "m3_search_advance": ([vp] * 6, i32),
             "m3_search_stats": ([vp, vp], i32),
             "m3_search_ucb1": ([vp, i64] + [vp] * 5, i32),
+            "m3_search_nn_create": ([vp, i64, i32, vp], i32),
+            "m3_search_nn_destroy": ([vp], i32),
+            "m3_search_nn_set_roots": ([vp, vp, vp, vp, vp], i32),
+            "m3_search_nn_batch": ([vp, i32, vp, vp], i32),
+            "m3_search_nn_feed_device": ([vp, vp, vp], i32),
+            "m3_search_nn_feed": ([vp, vp, vp], i32),
+            "m3_search_nn_run_linear": ([vp, i32, vp], i32),
+            "m3_search_nn_result": ([vp] * 10, i32),
+            "m3_search_nn_advance": ([vp] * 6, i32),
+            "m3_search_nn_stats": ([vp, vp], i32),
         }
         for name, (args, res) in sig.items():
             fn = getattr(L, name, None)  # (an older A/B build may lack newer entry points;

@@ -240,3 +240,41 @@ def search_lockstep(searches: Sequence[MCTS]):
             m.backpropagate(m._leaf, int(r[0]) if k == 1 else float(np.mean(r)))
             m._leaf = None
     return [m.finish() for m in searches]
+
+
+class NeuralNetworkMCTS:
+    """``mctslib.nn.mcts.NeuralNetworkMCTS(model, state, exploration_weight, simulations, verbose)``:
+    the batch-1 drop-in over the device trees (``match3tile.search.DeviceSearchNN`` with one game).
+
+    ``model(array[1, R, C]) -> (value, policy)`` as nn/mcts.py:46 calls it: ``policy`` holds one raw
+    logit per action once flattened. It is called once for every node that is created and is not
+    terminal. ``exploration_weight`` is kept for parity; selection uses the node's ``n_actions``
+    (abc/mcts.py:96). For many games at once use ``DeviceSearchNN`` itself."""
+
+    def __init__(self, model, state, exploration_weight: float, simulations: int, verbose: bool = False):
+        from .search import DeviceSearchNN
+
+        self.model = model
+        self._exploration_weight = exploration_weight
+        self._simulations = simulations
+        self._verbose = verbose
+        A = 2 * state.cfg.rows * (state.cfg.columns - 1)
+
+        def evaluator(boards, need):
+            values, logits = np.zeros(1, np.float32), np.zeros((1, A), np.float32)
+            if need[0]:
+                value, policy = model(np.asarray(boards[:1]))
+                values[0] = np.float32(np.asarray(value).reshape(-1)[0])
+                logits[0] = np.asarray(policy, dtype=np.float32).reshape(-1)[:A]
+            return values, logits
+
+        self._search = DeviceSearchNN([state], simulations, evaluator=evaluator)
+
+    @property
+    def state(self):
+        """The current root."""
+        return self._search.states()[0]
+
+    def __call__(self):
+        (action, value, policies), = self._search()
+        return action, value, policies

@@ -1,7 +1,8 @@
 """Episode scorers of the reference's ``samplerTasks.py`` over the device step, and batched greedy.
 
-``random_task`` / ``greedy_test`` / ``mcts_task`` restate samplerTasks.py:9-32
-(the NN variant, :35-42, needs the JAX model and is out of scope). The
+``random_task`` / ``greedy_test`` / ``mcts_task`` / ``nn_mcts_task`` restate samplerTasks.py:9-42
+(the NN variant takes any ``model(array[1, R, C]) -> (value, policy)``; the JAX net itself is out of
+scope), and ``nn_mcts_episodes`` plays many such episodes in lockstep on the device trees. The
 reference functions take no arguments and draw the board seed from numpy's
 global RNG (``BoardConfig()``, boardConfig.py:34); here ``seed`` may be given
 to make an episode reproducible, and ``None`` keeps the reference behaviour.
@@ -24,7 +25,7 @@ import numpy as np
 from . import _native
 from .boardConfig import BoardConfig
 from .boardv2 import BoardV2, _ids_past_board, _sync_global_rng
-from .mcts import MCTS
+from .mcts import MCTS, NeuralNetworkMCTS
 
 
 def _start(seed, moves=20):
@@ -57,6 +58,35 @@ def mcts_task(seed=None, exploration_weight=2, simulations=100) -> int:
         action, _, _ = search()
         state = state.apply_action(action)
     return state.reward
+
+
+def nn_mcts_task(model, seed=None, exploration_weight=3, simulations=100, moves=20) -> int:
+    """samplerTasks.py:35-42: NeuralNetworkMCTS(model, state, 3, 100) every move, trees on the device."""
+    state = _start(seed, moves)
+    search = NeuralNetworkMCTS(model, state, exploration_weight, simulations, verbose=False)
+    while not state.is_terminal:
+        action, _, _ = search()
+        state = state.apply_action(action)
+    return state.reward
+
+
+def nn_mcts_episodes(seeds, evaluator=None, weights=None, moves: int = 20, simulations: int = 100, rows: int = 9,
+                     columns: int = 9, types: int = 6):
+    """``nn_mcts_task`` for every seed at once, in lockstep: one ``DeviceSearchNN`` over all games, one
+    search and one re-rooting per move. ``evaluator`` / ``weights`` as ``DeviceSearchNN`` takes them
+    (a batch evaluator on the host, or the built-in linear evaluator on the device). Returns the episode
+    scores [len(seeds)]."""
+    from .search import DeviceSearchNN
+
+    seeds = [int(s) for s in np.atleast_1d(seeds)]
+    states = [BoardV2(moves, BoardConfig(rows=rows, columns=columns, types=types, seed=s)) for s in seeds]
+    ds = DeviceSearchNN(states, simulations, evaluator=evaluator, weights=weights)
+    try:
+        for _ in range(moves):
+            ds()
+        return np.array([s.reward for s in ds.states()], dtype=np.int64)
+    finally:
+        ds.close()
 
 
 def greedy_actions(states: Sequence[BoardV2], sync_rng: bool = False) -> List:

@@ -224,6 +224,85 @@ int m3_search_stats(m3_search *s, uint64_t out[4]);
 int m3_search_ucb1(m3_ctx *ctx, int64_t n, const int64_t *reward_sum, const int32_t *visits,
                    const int32_t *parent_visits, const double *c, double *out);
 
+/* ---- network-guided device MCTS trees (mctslib/nn/mcts.py: NNNode, NeuralNetworkMCTS) ---------- */
+/* n_games prior-weighted search trees in device memory, searched in lockstep, with the evaluator
+ * behind a split-phase call: a round runs up to an EVALUATION BATCH -- one board per game and a
+ * `need` byte -- and goes on once the caller has fed (value: f32, logits: f32[A]) for every game.
+ * The library keeps no ML framework in the process; an evaluator is anything that fills two device
+ * (or host) arrays. Semantics (csrc/m3_search_nn_core.hpp has the arithmetic, DESIGN.md §4.9 the
+ * reasons):
+ *   - every node that is created and is not terminal is evaluated once; the logits stay raw (no
+ *     softmax, they may be negative), entries of illegal actions are never read;
+ *   - a child's prior is its parent's logit at the child's action, the root's prior is 1.0;
+ *   - expansion pops the highest untried legal action, one expansion per game and round;
+ *   - score of a child with v visits under a parent with pv visits and c = the parent state's
+ *     n_actions: +inf if v == 0, else in float32, every operation rounded on its own,
+ *         sum / (f32)v + ((f32)c * prior) * (f32)sqrt(log(pv) / (double)(1 + v))
+ *     (the square root's argument in double, rounded to f32 once); first maximum in expansion order;
+ *   - backup: the evaluator's value for a new non-terminal child, (f32)state reward for a terminal
+ *     leaf or a terminal new child -- not reward plus value -- added in f32 from leaf to root (the
+ *     reference keeps an all-integer sum as an int; here it is always f32, exact below 2^24).
+ * This is this project's reading of what eager JAX does on float32; it has not been compared against
+ * JAX.
+ *
+ * Memory: node_capacity slots per game of 16 + 32 + 4 * ceil(A/32) + rows*columns + 4 * A bytes
+ * (9x9x6: 725, 16x16x8: 2,288), never compacted.
+ *
+ * A game freezes as in the UCB1 trees (M3_FLAG_NO_LEGAL, M3_FLAG_SHUFFLE_CAP / M3_FLAG_CASCADE_CAP of
+ * an expansion's step) and in one more case: a needed row whose value, or any logit of a legal
+ * action, is not finite gives M3_FLAG_BAD_EVAL; the node it was for is not linked, the tree stays as
+ * it stood. The other games go on.
+ *
+ * The batch protocol. After m3_search_nn_set_roots the first two batches are the construction's
+ * (abc/mcts.py:82): the roots themselves, then the child of each root's highest legal action; neither
+ * backs anything up. Every later batch is one simulation round. The library tracks the phase.
+ *   m3_search_nn_batch        enqueues the work up to the next batch and returns its device pointers:
+ *                             boards int8 [n][N], need uint8 [n] (1: the game created a non-terminal
+ *                             node this round; rows with need 0 are ignored when fed).
+ *   m3_search_nn_feed_device  values f32 [n], logits f32 [n][A] in device memory: enqueues the rest of
+ *   m3_search_nn_feed         the round. The host form stages the arrays and blocks until done.
+ * Everything runs on the context stream. Ordering contract for an evaluator on a foreign runtime or
+ * stream: m3_ctx_synchronize after m3_search_nn_batch and before reading the batch; the caller's own
+ * stream finished before m3_search_nn_feed_device (the library does not wait for it).
+ * M3_ERR_STATE: a feed without a pending batch, a second batch (or a result / advance / run_linear)
+ * while one is pending, any call before m3_search_nn_set_roots. */
+#define M3_FLAG_BAD_EVAL 0x400u /* search_nn: a needed evaluation (value or a legal logit) is not finite */
+typedef struct m3_search_nn m3_search_nn;
+int m3_search_nn_create(m3_ctx *ctx, int64_t n_games, int32_t node_capacity, m3_search_nn **out);
+int m3_search_nn_destroy(m3_search_nn *s);
+/* The root nodes, as m3_search_set_roots (a root with n_actions < 1 keeps no child and is never
+ * evaluated). Drops the trees the object held and any pending batch. The next batch is the roots'. */
+int m3_search_nn_set_roots(m3_search_nn *s, const int8_t *boards, const uint32_t *seeds, const int32_t *n_actions,
+                           const int32_t *rewards);
+/* remaining: the simulations the caller's run still has to go, this one included (ignored for the two
+ * construction batches). M3_ERR_CAP, with nothing enqueued and the trees untouched, unless
+ * used + remaining + 1 <= node_capacity, used = 1 + the simulation rounds fed since set_roots: passed
+ * truthfully, a run that does not fit is refused at its first batch. Does not wait for the kernels. */
+int m3_search_nn_batch(m3_search_nn *s, int32_t remaining, const int8_t **d_boards, const uint8_t **d_need);
+int m3_search_nn_feed_device(m3_search_nn *s, const float *d_values, const float *d_logits);
+int m3_search_nn_feed(m3_search_nn *s, const float *values, const float *logits);
+/* The built-in baseline evaluator, and a whole run with no host round trip: any pending construction
+ * batches and then `simulations` rounds, each batch evaluated on the device by a linear map of the
+ * one-hot board. d_W: device f32 [N][CH][A + 1], CH = 2^(ceil(log2(types)) + 2) (the reference's
+ * one-hot width, elementCrush.py:66, :92); a cell whose value is >= CH contributes nothing.
+ *     out[j] = (((W[0][x0][j] + W[1][x1][j]) + W[2][x2][j]) + ...) over the cells in ascending order,
+ * float32, no bias; logits = out[0 .. A), value = out[A]. M3_ERR_CAP as m3_search_nn_batch with
+ * remaining = simulations. Does not wait for the kernels; d_W must stay valid until they are done. */
+int m3_search_nn_run_linear(m3_search_nn *s, int32_t simulations, const float *d_W);
+/* As m3_search_result, with child_value_sum (f32) in place of child_reward, and child_prior (f32).
+ * value is still the integer state reward at the end of the greedy line (c = 0 in the score). */
+int m3_search_nn_result(m3_search_nn *s, int32_t *best_action, int32_t *value, int32_t *root_visits,
+                        int32_t *n_children, int32_t *child_action, int32_t *child_visits, float *child_value_sum,
+                        float *child_prior, uint32_t *flags);
+/* As m3_search_advance. */
+int m3_search_nn_advance(m3_search_nn *s, const int32_t *actions, int8_t *out_boards, int32_t *out_rewards,
+                         int32_t *out_n_actions, uint32_t *out_legal_bits);
+/* Since m3_search_nn_set_roots: out[0] node slots used (the maximum over the games, as of the last
+ * result), out[1] simulation rounds fed, out[2] expansions recomputed by the apply kernel's exact
+ * pass, out[3] batches fed from host arrays, out[4] from device arrays, out[5] evaluated by the
+ * built-in linear evaluator. Blocks. */
+int m3_search_nn_stats(m3_search_nn *s, uint64_t out[6]);
+
 /* ---- device-resident batched env: n x Match3Env (env.py:8-65) ----------- */
 
 /* num_moves / env_goal as Match3Env(num_moves=20, env_goal=500) (env.py:15-16). */
