@@ -27,8 +27,10 @@
 //     w     = (f32)c * prior
 //     score = mean + w * e
 //   visits == 0 gives +inf and nothing else is evaluated; c == 0 (the greedy line) still evaluates the
-//   product. First maximum in expansion order, strict `>`. This is this project's reading of what
-//   eager JAX does on float32; it has not been compared against JAX.
+//   product. First maximum in expansion order, strict `>`.
+//   The trees are pinned to the reference's own tree code. It is executed with numpy standing in for
+//   `jax.numpy` and with integer rewards handed over as Python ints, so that numpy promotes as JAX does
+//   with x64 off. JAX itself has still not been run. (tests/golden/gen_golden_search_nn.py)
 //
 // Backup: ret = the evaluator's value for a new non-terminal child, (f32)state_reward for a terminal
 // leaf or a terminal new child (nn/mcts.py:52-56) -- not reward plus value; sum += ret in f32 from

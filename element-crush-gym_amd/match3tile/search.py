@@ -232,8 +232,10 @@ class DeviceSearchNN:
 
     The logits stay raw (no softmax; they may be negative); a child's prior is its parent's logit at
     the child's action; the value of a new non-terminal child -- the state reward of a terminal one --
-    is backed up as float32. The arithmetic is in csrc/m3_search_nn_core.hpp; it is this project's
-    reading of eager JAX on float32 and has not been compared against JAX.
+    is backed up as float32. The arithmetic is in csrc/m3_search_nn_core.hpp. The trees are pinned to
+    the reference's own tree code. It is executed with numpy standing in for ``jax.numpy`` and with
+    integer rewards handed over as Python ints, so that numpy promotes as JAX does with x64 off. JAX
+    itself has still not been run.
 
     An already-terminal root behaves as documented for ``DeviceSearch``. ``node_capacity`` defaults to
     ``2 + max(n_actions) * simulations``; a slot is 16 + 32 + 4 * ceil(A / 32) + rows * columns + 4 * A

@@ -242,8 +242,9 @@ int m3_search_ucb1(m3_ctx *ctx, int64_t n, const int64_t *reward_sum, const int3
  *   - backup: the evaluator's value for a new non-terminal child, (f32)state reward for a terminal
  *     leaf or a terminal new child -- not reward plus value -- added in f32 from leaf to root (the
  *     reference keeps an all-integer sum as an int; here it is always f32, exact below 2^24).
- * This is this project's reading of what eager JAX does on float32; it has not been compared against
- * JAX.
+ * The trees are pinned to the reference's own tree code. It is executed with numpy standing in for
+ * `jax.numpy` and with integer rewards handed over as Python ints, so that numpy promotes as JAX does
+ * with x64 off. JAX itself has still not been run.
  *
  * Memory: node_capacity slots per game of 16 + 32 + 4 * ceil(A/32) + rows*columns + 4 * A bytes
  * (9x9x6: 725, 16x16x8: 2,288), never compacted.

@@ -64,6 +64,14 @@ class HostSearchNN:
         self.h = lib().nh_create(self.n, self.cap, self.N, self.AW, self.A)
         self.ev, self.rec = evaluator, record
         self._rec([self.n, self.cap, self.N, self.AW, self.A])
+        self.set_roots(states)
+
+    def set_roots(self, states, evaluator=None):
+        """nh_set_roots (again: the trees the object held are dropped), then the two construction batches."""
+        assert len(states) == self.n
+        if evaluator is not None:
+            self.ev = evaluator
+        oracle = self.o
         self.seeds = [int(s.cfg.seed) for s in states]
         boards = np.ascontiguousarray(np.stack([np.asarray(s.array).reshape(-1) for s in states]), dtype=np.int8)
         na = np.array([s.n_actions for s in states], np.int32)

@@ -1,7 +1,10 @@
 """Expected side of the network-guided device trees (``m3_search_nn_*``, ``DeviceSearchNN``): a Python
 model written from the semantics of include/m3.h and DESIGN.md §4.9 -- not from the library's code --
 over the C oracle's step (``search_ref.FreezingBoard``), with ``np.float32`` arithmetic, ``math.log``
-and ``math.sqrt``. Values are compared as bit patterns.
+and ``math.sqrt``. Values are compared as bit patterns. The model itself is held to the reference's own
+tree code by tests/test_search_nn_golden_cpu.py (tests/golden/search_nn.npz); it stays the expected
+side where the reference raises or never returns: frozen games (case G) and evaluations that are not
+finite (cases H, P, Q, R). The evaluators live in tests/nn_evaluators.py and are re-exported here.
 
 An evaluator here is ``ev(board[R, C], game, round) -> (value f32, logits f32[A])``; round 0 is the
 roots' batch, round 1 the construction's expansion, round 2 + k simulation k since the roots were set.
@@ -18,6 +21,7 @@ for p in (os.path.join(ROOT, "oracle"), os.path.join(ROOT, "element-crush-gym_am
         sys.path.insert(0, p)
 
 import search_ref  # noqa: E402
+from nn_evaluators import constant_ev, linear_eval, negative_ev, onehot_width, weights  # noqa: E402,F401
 from search_ref import F_NO_LEGAL, Freeze  # noqa: E402
 
 F_BAD_EVAL = 0x400
@@ -27,31 +31,6 @@ INF = f32(np.inf)
 
 def bits(x):
     return int(np.asarray(x, dtype=np.float32).reshape(()).view(np.uint32))
-
-
-def onehot_width(types):
-    return 2 ** (int(math.ceil(math.log2(types))) + 2)
-
-
-def weights(shape, k):
-    """W [N][CH][A + 1] of the linear evaluator, from RandomState(k)."""
-    R, C, T = shape
-    A = R * (C - 1) * 2
-    return np.random.RandomState(k).standard_normal((R * C, onehot_width(T), A + 1)).astype(np.float32)
-
-
-def linear_eval(W, board):
-    """out[j] = (((W[0][x0][j] + W[1][x1][j]) + ...): a sequential float32 loop over the cells, vectorised
-    over j only. A cell >= CH contributes nothing. Returns (value, logits)."""
-    CH, A = W.shape[1], W.shape[2] - 1
-    acc = None
-    for i, x in enumerate(np.asarray(board).reshape(-1)):
-        x = int(x)
-        if 0 <= x < CH:
-            acc = W[i, x].copy() if acc is None else (acc + W[i, x]).astype(np.float32)
-    if acc is None:
-        acc = np.zeros(A + 1, np.float32)
-    return f32(acc[A]), acc[:A].copy()
 
 
 def linear_evaluator(W):
@@ -281,16 +260,6 @@ def case_e():
                 want=run_case("E", shape, roots, 40, 2, linear_evaluator(W)))
 
 
-def constant_ev(board, game, rnd):
-    return f32(0.0), np.ones(2 * board.shape[0] * (board.shape[1] - 1), np.float32)
-
-
-def negative_ev(board, game, rnd):
-    """All logits negative, distinct per action; the value depends on the board."""
-    A = 2 * board.shape[0] * (board.shape[1] - 1)
-    return f32(int(np.asarray(board).sum()) % 7) * f32(0.25), (-(np.arange(A) % 5) - f32(0.5)).astype(np.float32)
-
-
 def case_f(which):
     shape = (9, 9, 6)
     roots = search_ref.reset_roots(range(901, 909), 3)
@@ -318,3 +287,118 @@ def case_h():
         value, logits = base(board, game, rnd)
         return (f32(np.nan), logits) if (game == H_GAME and rnd == H_ROUND) else (value, logits)
     return dict(a, ev=ev, want=run_case("H", a["shape"], a["roots"], a["sims"], a["calls"], ev))
+
+
+# ---- non-finite logits: cases P (one poisoned legal logit per game), Q (every illegal logit) and R
+# (an infinite weight of the linear evaluator), all on the roots of case A --------------------------
+NAN, FLT_MAX, DENORMAL = f32(np.nan), np.finfo(np.float32).max, f32(1e-45)
+
+
+def trace_case_a():
+    """The clean run of case A again, with every evaluation written down:
+    {(game, round): (board, legal ids ascending)}. The model's own record: nothing of the library."""
+    if "A-trace" in _cache:
+        return _cache["A-trace"][1]
+    a = case_a()
+    o = search_ref.capped_oracle(a["shape"])
+    trace = {}
+
+    def ev(board, game, rnd):
+        assert (game, rnd) not in trace
+        trace[(game, rnd)] = (np.array(board, np.int32), sorted(int(x) for x in o.legal_actions(np.array(board, np.int32))))
+        return a["ev"](board, game, rnd)
+    want = run_case("A-trace-run", a["shape"], a["roots"], a["sims"], a["calls"], ev)
+    assert want == a["want"]
+    _cache["A-trace"] = (want, trace)
+    return trace
+
+
+def _first(pred):
+    return lambda legal: next((x for x in legal if pred(x)), None)
+
+
+# kind: (rounds searched, games searched, the legal id poisoned, the value written, freezes)
+_SIMS_A, _CALLS_A = 20, 3
+POISON_KINDS = {
+    "nan_lowest": (range(2 + 4, 2 + _SIMS_A), range(18), lambda legal: legal[0], NAN, True),
+    "pinf_highest": (range(2 + _SIMS_A + 2, 2 + 2 * _SIMS_A), range(18), lambda legal: legal[-1], INF, True),  # in call 1
+    "ninf_ge128": (range(2 + 2, 2 + _SIMS_A), range(18), _first(lambda x: x >= 128), -INF, True),
+    "nan_mod31": (range(2 + 5, 2 + _SIMS_A * _CALLS_A), range(18), _first(lambda x: x % 32 == 31), NAN, True),
+    "nan_mod0": (range(2 + 7, 2 + _SIMS_A * _CALLS_A), range(18), _first(lambda x: x % 32 == 0), NAN, True),
+    "nan_roots": ([0], range(16, -1, -1), lambda legal: legal[len(legal) // 2], NAN, True),      # (the ragged workgroup)
+    "ninf_construction": ([1], range(17, -1, -1), lambda legal: legal[0], -INF, True),
+    "fltmax": ([0], range(18), lambda legal: legal[-1], FLT_MAX, False),       # the root's highest legal id: the first
+    "denormal": ([0], range(18), lambda legal: legal[-1], DENORMAL, False),    # child's prior, read in every selection
+}
+
+
+def pick_poisons():
+    """{kind: (game, round, id, value)}: for every kind the first game (one game per kind) and round of
+    the clean run whose evaluated node has such a legal id. A kind without one is missing."""
+    trace, taken, out = trace_case_a(), set(), {}
+    for kind, (rounds, games, pick, value, _) in POISON_KINDS.items():
+        for g in games:
+            hit = next(((rnd, pick(trace[(g, rnd)][1])) for rnd in rounds
+                        if (g, rnd) in trace and trace[(g, rnd)][1] and pick(trace[(g, rnd)][1]) is not None), None)
+            if g not in taken and hit is not None:
+                out[kind] = (g, hit[0], hit[1], value)
+                taken.add(g)
+                break
+    return out
+
+
+def case_p():
+    """Case A with one legal logit of one evaluated row poisoned in each of nine games."""
+    a, poisons = case_a(), pick_poisons()
+    at = {(g, rnd): (i, v) for g, rnd, i, v in poisons.values()}
+
+    def ev(board, game, rnd):
+        value, logits = a["ev"](board, game, rnd)
+        if (game, rnd) in at:
+            logits = logits.copy()
+            logits[at[(game, rnd)][0]] = at[(game, rnd)][1]
+        return value, logits
+    return dict(a, ev=ev, poisons=poisons, want=run_case("P", a["shape"], a["roots"], a["sims"], a["calls"], ev))
+
+
+def case_q():
+    """Case A with NaN, +inf and -inf written to every illegal id of every evaluated row: never read."""
+    a = case_a()
+    o = search_ref.capped_oracle(a["shape"])
+    junk = np.array([NAN, INF, -INF], np.float32)
+
+    def ev(board, game, rnd):
+        value, logits = a["ev"](board, game, rnd)
+        legal = set(int(x) for x in o.legal_actions(np.array(board, np.int32)))
+        illegal = np.array([i for i in range(len(logits)) if i not in legal])
+        logits = logits.copy()
+        logits[illegal] = junk[(illegal + game + rnd) % 3]
+        return value, logits
+    return dict(a, ev=ev, want=run_case("Q", a["shape"], a["roots"], a["sims"], a["calls"], ev))
+
+
+def pick_infinite_weight():
+    """(cell, cell value, logit id, games frozen, games hit only where the id is illegal, games never hit)
+    for W[cell][value][id] = +inf: the first choice, from the clean run's record, that freezes some
+    games, leaves some whose boards hit the weight only where the id is illegal, and misses some."""
+    trace = trace_case_a()
+    for cell in (72, 76, 80, 36, 40, 44, 0):
+        for x in range(1, 7):
+            hits = [(g, legal) for (g, _), (board, legal) in trace.items() if board.reshape(-1)[cell] == x]
+            hit_games = {g for g, _ in hits}
+            for j in range(144):
+                frozen = {g for g, legal in hits if j in legal}
+                if 3 <= len(frozen) <= 12 and len(hit_games - frozen) >= 2 and 18 - len(hit_games) >= 2:
+                    return cell, x, j, sorted(frozen), sorted(hit_games - frozen), sorted(set(range(18)) - hit_games)
+    return None
+
+
+def case_r():
+    """Case A with one weight of the linear evaluator +inf: the device's own evaluator produces the
+    infinite logit (and NaN where the sum goes on to add -inf: it does not here, one weight only)."""
+    a = case_a()
+    cell, x, j = pick_infinite_weight()[:3]
+    W = a["W"].copy()
+    W[cell, x, j] = INF
+    ev = linear_evaluator(W)
+    return dict(a, W=W, ev=ev, want=run_case("R", a["shape"], a["roots"], a["sims"], a["calls"], ev))

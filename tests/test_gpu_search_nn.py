@@ -3,8 +3,9 @@
 Bar: for every game of a lockstep batch and every call, the device trees hold what the Python model of
 search_nn_ref.py holds -- every root child's action, visits, value sum and prior (floats as bit
 patterns), the root's visits, the action, the value and the policies -- with the evaluator fed from
-the host (cases A, C..H) and with the built-in linear evaluator on the device (case B, which must
-equal case A bit for bit), and once with the answer handed over as device pointers.
+the host (cases A, C..H, and P, Q, R: rows with a logit that is not finite) and with the built-in
+linear evaluator on the device (case B, which must equal case A bit for bit), and with the answer
+handed over as device pointers.
 tests/test_search_nn_cpu.py runs the same cases on the host build first.
 """
 import ctypes
@@ -131,6 +132,57 @@ def test_case_h_bad_evaluation_freezes_one_game():
     with pytest.raises(RuntimeError, match="BAD_EVAL"):
         ds()
     ds.close()
+
+
+def test_case_p_one_poisoned_legal_logit_freezes_exactly_that_game():
+    """nn_store_row on the device: lanes stride the row by 64, lanes 0..15 make a third pass over ids
+    128..143, and a lane reads bit id & 31 of word id >> 5 of the node's legal set. One game each with NaN
+    / +inf / -inf at its lowest, its highest, a third-pass and two word-edge legal ids, in the roots'
+    batch and in the construction's, freezes with exactly M3_FLAG_BAD_EVAL; FLT_MAX and a denormal do
+    not. (tests/test_search_nn_cpu.py asserts that the model's games hold these conditions.)"""
+    p = ref.case_p()
+    assert set(p["poisons"]) == set(ref.POISON_KINDS)
+    for kind, (g, rnd, i, v) in p["poisons"].items():
+        assert p["want"][g][-1]["flags"] == (ref.F_BAD_EVAL if ref.POISON_KINDS[kind][4] else 0), kind
+    run_case(p)[0].close()
+
+
+def test_case_p_through_feed_device():
+    """The same poisoned rows handed over as device pointers (m3_search_nn_feed_device)."""
+    import search_nn_golden as gold
+    p = ref.case_p()
+    n, A, rounds = 18, 144, p["calls"] * p["sims"]
+    ev = ref.batch_evaluator(p["ev"], n, A)
+    ds = DeviceSearchNN(roots_of(p), p["sims"], evaluator=False, node_capacity=2 + rounds)
+    d_v, d_l = ds._ctx.device_empty(n * 4), ds._ctx.device_empty(n * A * 4)
+    for call in range(p["calls"]):
+        gold.feed_device_rounds(ds, ev, d_v, d_l, p["sims"], call == 0)
+        res = ds.result()
+        for g in range(n):
+            ref.assert_game(res, g, p["want"][g][call], ("feed_device", call))
+        ds.advance(None)
+    st = ds.stats()
+    assert st["device_feeds"] == 2 + rounds and st["host_feeds"] == 0 and st["rounds"] == rounds
+    ds.close()
+    d_v.free()
+    d_l.free()
+
+
+def test_case_q_illegal_logits_are_never_read():
+    """NaN and +-inf at every illegal id of every needed row of every round: equal to clean case A."""
+    a, q = ref.case_a(), ref.case_q()
+    assert q["want"] == a["want"]
+    run_case(q)[0].close()
+
+
+def test_case_r_infinite_weight_on_the_device_linear_path():
+    """One weight +inf: k_nn_linear itself produces the infinite logit. The games whose evaluated boards
+    meet it where the id is legal freeze, on the device's evaluator and host-fed alike."""
+    r = ref.case_r()
+    frozen = ref.pick_infinite_weight()[3]
+    assert [g for g in range(18) if r["want"][g][-1]["flags"] == ref.F_BAD_EVAL] == frozen and 3 <= len(frozen) <= 12
+    run_case(r, device_linear=True)[0].close()
+    run_case(r)[0].close()
 
 
 def test_feed_device_equals_host_feed():

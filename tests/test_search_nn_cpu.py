@@ -2,7 +2,8 @@
 
 tests/search_nn_host builds the M3_HD functions the tree kernels call for the host; the step between
 them is the C oracle's, the evaluator a Python function. Expected side: the Python model of
-search_nn_ref.py, written from the documented semantics. Every case of tests/test_gpu_search_nn.py
+search_nn_ref.py, written from the documented semantics (tests/test_search_nn_golden_cpu.py holds the
+model and this host build to the reference's own tree code). Every case of tests/test_gpu_search_nn.py
 runs here first, compared as bit patterns; the score and the linear evaluator are checked on their own.
 """
 import math
@@ -105,6 +106,87 @@ def test_case_h_bad_evaluation_freezes_one_game():
     # the tree as it stood: four simulations backed up, the fifth's node not linked
     assert h["want"][ref.H_GAME][0]["root_visits"] == 4
     run_case(h)
+
+
+# ---- the legal-logit finiteness check (nn_store_row, the `bad` of nn_commit) ---------------------
+def test_case_p_one_poisoned_legal_logit_freezes_exactly_that_game():
+    """NaN / +inf / -inf at the lowest and the highest legal id, at a legal id >= 128 (the third pass
+    over the row), at legal ids with id % 32 == 31 and == 0 (the word edges of the legal bits), in the
+    roots' batch and in the construction's; FLT_MAX and a denormal, which are finite."""
+    a, p = ref.case_a(), ref.case_p()
+    poisons = p["poisons"]
+    assert set(poisons) == set(ref.POISON_KINDS), sorted(set(ref.POISON_KINDS) - set(poisons))  # every condition exists
+    trace = ref.trace_case_a()
+    assert len({g for g, _, _, _ in poisons.values()}) == len(poisons)
+    for kind, (g, rnd, i, v) in poisons.items():
+        legal = trace[(g, rnd)][1]
+        assert i in legal and p["ev"](trace[(g, rnd)][0], g, rnd)[1].view(np.uint32)[i] == ref.bits(v), kind
+        freezes = ref.POISON_KINDS[kind][4]
+        assert freezes == (not np.isfinite(v)), kind
+        call0 = max(0, rnd - 2) // p["sims"]  # the call whose result first shows it
+        for call in range(3):
+            w = p["want"][g][call]
+            if call < call0:
+                assert w == a["want"][g][call], (kind, call)
+            else:
+                assert w["flags"] == (ref.F_BAD_EVAL if freezes else 0), (kind, call, hex(w["flags"]))
+    g, rnd, i, _ = poisons["nan_lowest"]
+    assert i == trace[(g, rnd)][1][0] and rnd >= 2
+    g, rnd, i, _ = poisons["pinf_highest"]
+    assert i == trace[(g, rnd)][1][-1] and rnd >= 2 + p["sims"]  # in the second call: the first is clean
+    assert p["want"][g][0]["flags"] == 0 and p["want"][g][1]["root_visits"] >= 1
+    assert poisons["ninf_ge128"][2] >= 128 and poisons["ninf_ge128"][1] >= 2
+    assert poisons["nan_mod31"][2] % 32 == 31 and poisons["nan_mod0"][2] % 32 == 0
+    assert poisons["nan_mod31"][1] >= 2 and poisons["nan_mod0"][1] >= 2
+    # the roots' batch: no child, no visit; the construction's: the child never linked, the tree as it stood
+    for kind, rnd in (("nan_roots", 0), ("ninf_construction", 1)):
+        g = poisons[kind][0]
+        assert poisons[kind][1] == rnd and g >= 16, kind  # (in the ragged second workgroup of the device)
+        assert all(w == dict(children=[], root_visits=0, flags=ref.F_BAD_EVAL) for w in p["want"][g]), kind
+    # a simulation round: the tree as it stood, the rounds before it backed up
+    g, rnd = poisons["nan_lowest"][:2]
+    assert p["want"][g][0]["root_visits"] == rnd - 2 and len(p["want"][g][0]["children"]) >= 1
+    # finite, however large or small: the tree goes on (and is the model's, not case A's)
+    assert any(p["want"][poisons[k][0]] != a["want"][poisons[k][0]] for k in ("fltmax", "denormal"))
+    # every other game is untouched
+    others = set(range(18)) - {g for g, _, _, _ in poisons.values()}
+    assert len(others) == 9 and all(p["want"][g] == a["want"][g] for g in others)
+    run_case(p)
+
+
+def test_case_q_illegal_logits_are_never_read():
+    """NaN and +-inf at every illegal id of every needed row of every round: nothing freezes and every
+    tree equals clean case A bit for bit."""
+    a, q = ref.case_a(), ref.case_q()
+    trace = ref.trace_case_a()
+    (g, rnd), (board, legal) = next(iter(trace.items()))
+    row = q["ev"](board, g, rnd)[1]
+    assert all(np.isfinite(row[i]) == (i in legal) for i in range(144)) and 0 < len(legal) < 144
+    assert q["want"] == a["want"] and all(not w[-1]["flags"] for w in q["want"])
+    run_case(q)
+
+
+def test_case_r_infinite_weight_of_the_linear_evaluator():
+    """W[cell][x][j] = +inf: the games whose evaluated boards hold x at the cell where j is legal freeze,
+    the ones that hold it only where j is illegal and the ones that never hold it equal case A."""
+    a, r = ref.case_a(), ref.case_r()
+    cell, x, j, frozen, hit_only, missed = ref.pick_infinite_weight()
+    assert len(frozen) >= 3 and len(hit_only) >= 2 and len(missed) >= 2
+    assert [g for g in range(18) if r["want"][g][-1]["flags"]] == frozen
+    assert all(r["want"][g][-1]["flags"] == ref.F_BAD_EVAL for g in frozen)
+    assert all(r["want"][g] == a["want"][g] for g in hit_only + missed)
+    run_case(r)
+    # the host build of the device's evaluator gives the model's infinity (and NaN once -inf is added to it)
+    L = nh.lib()
+    W = r["W"].copy()
+    board = np.full(81, x, np.int8)
+    for trial in range(2):
+        value, logits = np.zeros(1, np.float32), np.zeros(144, np.float32)
+        L.nh_linear(nh._p(board), nh._p(W), 81, W.shape[1], 144, nh._p(value), nh._p(logits))
+        wv, wl = ref.linear_eval(W, board)
+        assert ref.bits(value[0]) == ref.bits(wv) and np.array_equal(logits.view(np.uint32), wl.view(np.uint32))
+        assert (np.isnan(wl[j]) if trial else wl[j] == np.inf) and np.isfinite(np.delete(wl, j)).all()
+        W[cell + 1, x, j] = -np.inf
 
 
 def test_capacity_and_order_of_calls():
