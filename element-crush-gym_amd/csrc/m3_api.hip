@@ -1,6 +1,7 @@
 // m3_api.hip -- the C ABI of include/m3.h (kernels and launchers: m3_kernels.hpp).
 #include "m3_kernels.hpp"
 #include "m3_search.hpp"
+#include "m3_net.hpp"
 #include "m3_search_nn.hpp"
 
 #include <string>
@@ -1553,6 +1554,221 @@ int m3_search_ucb1(m3_ctx* c, int64_t n, const int64_t* reward_sum, const int32_
 
 }  // extern "C"
 
+// ---- the policy/value network (m3_net.hpp: the kernels; m3_net_core.hpp: folding and pre-pack) ------
+struct m3_net {
+    m3_ctx* ctx = nullptr;
+    int L = 0;
+    m3n::NetShape S{};
+    float *stem_w = nullptr, *stem_b = nullptr;
+    std::vector<uint16_t*> conv_w;  // 2L packed B operands
+    std::vector<float*> conv_b;
+    m3n::NetHeads H{};
+    uint16_t* act[2] = {nullptr, nullptr};  // the workspace: two activation buffers of `chunk` boards
+    int64_t chunk = 0;
+    std::vector<void*> owned;
+};
+
+namespace {
+
+// the workspace holds at most this many activation elements per buffer (64 MiB of bf16 each)
+constexpr int64_t NET_WORK_ELEMS = (int64_t)1 << 25;
+
+// stem and `layers` residual layers of n <= chunk boards: the result is in net->act[0]
+int enqueue_net_trunk(m3_net* net, const int8_t* d_boards, int64_t n, int layers) {
+    hipStream_t st = net->ctx->stream;
+    HIP_TRY(m3n::launch_net_stem(st, net->S, n, d_boards, net->stem_w, net->stem_b, net->act[0]));
+    for (int i = 0; i < layers; ++i) {
+        HIP_TRY(m3n::launch_net_conv(st, net->S, n, net->act[0], net->conv_w[2 * i], net->conv_b[2 * i], nullptr,
+                                     net->act[1]));
+        HIP_TRY(m3n::launch_net_conv(st, net->S, n, net->act[1], net->conv_w[2 * i + 1], net->conv_b[2 * i + 1],
+                                     net->act[0], net->act[0]));
+    }
+    return M3_OK;
+}
+
+// the whole network on n boards in device memory, chunk by chunk through the workspace
+int enqueue_net_forward(m3_net* net, const int8_t* d_boards, const uint8_t* d_need, int64_t n, float* d_values,
+                        float* d_logits) {
+    for (int64_t b0 = 0; b0 < n; b0 += net->chunk) {
+        const int64_t nb = std::min(net->chunk, n - b0);
+        int rc = enqueue_net_trunk(net, d_boards + b0 * net->S.P, nb, net->L);
+        if (rc) return rc;
+        HIP_TRY(m3n::launch_net_heads(net->ctx->stream, net->S, nb, net->act[0], net->H, d_need ? d_need + b0 : nullptr,
+                                      d_values + b0, d_logits + b0 * net->S.A));
+    }
+    return M3_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int m3_net_destroy(m3_net* net) {
+    if (!net) return M3_OK;
+    (void)hipSetDevice(net->ctx->device);
+    (void)hipStreamSynchronize(net->ctx->stream);
+    for (void* p : net->owned) (void)hipFree(p);
+    delete net;
+    return M3_OK;
+}
+
+int m3_net_create(m3_ctx* c, int32_t rows, int32_t columns, int32_t types, int32_t layers, int32_t features,
+                  double bn_eps, const float* blob, int64_t blob_len, m3_net** out) {
+    CHECK_ARG(c && out && blob, "bad arguments");
+    *out = nullptr;
+    CHECK_ARG(rows == c->R && columns == c->C && types == c->T, "the network's board shape is not the context's");
+    CHECK_ARG(layers >= 0 && bn_eps >= 0.0, "layers < 0 or bn_eps < 0");
+    int rc = check_ids_on_board(c);
+    if (rc) return rc;
+    if (!m3n::net_features_ok(features))
+        return set_err(M3_ERR_UNSUPPORTED, "features = %d: a multiple of 32 in %d..%d is supported", features,
+                       m3n::NET_MIN_F, m3n::NET_MAX_F);
+    const int P = c->N, A = c->A, CH = m3s::nn_onehot_width(c->T), F = features, L = layers;
+    const int64_t want = m3n::net_blob_len(P, A, CH, L, F);
+    if (blob_len != want)
+        return set_err(M3_ERR_INVALID, "weight blob of %lld floats, expected %lld", (long long)blob_len, (long long)want);
+    HIP_TRY(hipSetDevice(c->device));
+    m3_net* net = new m3_net;
+    net->ctx = c;
+    net->L = L;
+    net->S = m3n::NetShape{c->R, c->C, P, A, CH, F};
+    net->chunk = std::max<int64_t>(1, NET_WORK_ELEMS / ((int64_t)P * F));
+    hipError_t err = hipSuccess;
+    auto upload = [&](const void* host, size_t bytes) -> void* {
+        void* d = nullptr;
+        if (err == hipSuccess) err = hipMalloc(&d, bytes);
+        if (err != hipSuccess) return nullptr;
+        net->owned.push_back(d);
+        err = hipMemcpy(d, host, bytes, hipMemcpyHostToDevice);
+        return d;
+    };
+    const float* p = blob;
+    auto take = [&](int64_t count) {
+        const float* q = p;
+        p += count;
+        return q;
+    };
+    // a convolution with its BN, in the blob's order: kernel, bias, bn.{scale, bias, mean, var}
+    struct Conv {
+        const float *w, *b, *scale, *bias, *mean, *var;
+    };
+    auto take_conv = [&](int64_t rows_, int outs) {
+        Conv k;
+        k.w = take(rows_ * outs);
+        k.b = take(outs);
+        k.scale = take(outs);
+        k.bias = take(outs);
+        k.mean = take(outs);
+        k.var = take(outs);
+        return k;
+    };
+    std::vector<float> wf, bf;
+    auto fold_f32 = [&](const Conv& k, int64_t rows_, int outs, const float** d_w, const float** d_b) {
+        wf.resize((size_t)rows_ * outs);
+        bf.resize(outs);
+        m3n::net_fold_conv_f32(k.w, k.b, k.scale, k.bias, k.mean, k.var, bn_eps, rows_, outs, wf.data(), bf.data());
+        *d_w = (const float*)upload(wf.data(), wf.size() * 4);
+        *d_b = (const float*)upload(bf.data(), bf.size() * 4);
+    };
+    {
+        const Conv k = take_conv((int64_t)9 * CH, F);
+        const float *w = nullptr, *b = nullptr;
+        fold_f32(k, (int64_t)9 * CH, F, &w, &b);
+        net->stem_w = const_cast<float*>(w);
+        net->stem_b = const_cast<float*>(b);
+    }
+    std::vector<uint16_t> wh((size_t)9 * F * F), wpk((size_t)9 * F * F);
+    for (int i = 0; i < 2 * L; ++i) {
+        const Conv k = take_conv((int64_t)9 * F, F);
+        bf.resize(F);
+        m3n::net_fold_conv_bf16(k.w, k.b, k.scale, k.bias, k.mean, k.var, bn_eps, (int64_t)9 * F, F, wh.data(), bf.data());
+        m3n::net_pack(F, wh.data(), wpk.data());
+        net->conv_w.push_back((uint16_t*)upload(wpk.data(), wpk.size() * 2));
+        net->conv_b.push_back((float*)upload(bf.data(), bf.size() * 4));
+    }
+    {
+        const Conv k = take_conv(F, 1);
+        fold_f32(k, F, 1, &net->H.v_w, &net->H.v_b);
+        const float* d1w = take((int64_t)P * F);
+        const float* d1b = take(F);
+        const float* d2w = take(F);
+        const float* d2b = take(1);
+        net->H.d1_w = (const float*)upload(d1w, (size_t)P * F * 4);
+        net->H.d1_b = (const float*)upload(d1b, (size_t)F * 4);
+        net->H.d2_w = (const float*)upload(d2w, (size_t)F * 4);
+        net->H.d2_b = (const float*)upload(d2b, 4);
+    }
+    {
+        const Conv k = take_conv(F, 2);
+        fold_f32(k, F, 2, &net->H.p_w, &net->H.p_b);
+        const float* pw = take((int64_t)2 * P * A);
+        const float* pb = take(A);
+        net->H.pd_w = (const float*)upload(pw, (size_t)2 * P * A * 4);
+        net->H.pd_b = (const float*)upload(pb, (size_t)A * 4);
+    }
+    for (uint16_t*& a : net->act) {
+        void* d = nullptr;
+        if (err == hipSuccess) err = hipMalloc(&d, (size_t)net->chunk * P * F * 2);
+        if (err == hipSuccess) net->owned.push_back(d);
+        a = (uint16_t*)d;
+    }
+    if (err != hipSuccess) {
+        m3_net_destroy(net);
+        return set_err(M3_ERR_HIP, "net allocation (%d layers x %d features): %s", L, F, hipGetErrorString(err));
+    }
+    *out = net;
+    return M3_OK;
+}
+
+int m3_net_forward_device(m3_net* net, const int8_t* d_boards, const uint8_t* d_need, int64_t n, float* d_values,
+                          float* d_logits) {
+    CHECK_ARG(net && n >= 0, "bad arguments");
+    if (n == 0) return M3_OK;
+    CHECK_ARG(d_boards && d_values && d_logits, "null device array");
+    HIP_TRY(hipSetDevice(net->ctx->device));
+    return enqueue_net_forward(net, d_boards, d_need, n, d_values, d_logits);
+}
+
+int m3_net_forward(m3_net* net, const int8_t* boards, int64_t n, float* values, float* logits) {
+    CHECK_ARG(net && n >= 0, "bad arguments");
+    if (n == 0) return M3_OK;
+    CHECK_ARG(boards && values && logits, "null array");
+    m3_ctx* c = net->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    HostCall hc(c);
+    const int i_b = hc.input(boards, (size_t)n * c->N);
+    const int o_v = hc.output(values, (size_t)n * 4), o_l = hc.output(logits, (size_t)n * c->A * 4);
+    int rc = hc.begin(false, 0, 0);
+    if (rc) return rc;
+    rc = enqueue_net_forward(net, hc.dev<const int8_t>(i_b), nullptr, n, hc.dev<float>(o_v), hc.dev<float>(o_l));
+    if (rc) return rc;
+    return hc.finish();
+}
+
+int m3_net_trunk(m3_net* net, const int8_t* boards, int64_t n, int32_t upto, float* out) {
+    CHECK_ARG(net && n >= 0, "bad arguments");
+    CHECK_ARG(upto >= 0 && upto <= net->L, "upto outside [0, layers]");
+    if (n == 0) return M3_OK;
+    CHECK_ARG(boards && out, "null array");
+    m3_ctx* c = net->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const int64_t per = (int64_t)c->N * net->S.F;
+    HostCall hc(c);
+    const int i_b = hc.input(boards, (size_t)n * c->N);
+    const int o_x = hc.output(out, (size_t)n * per * 4);
+    int rc = hc.begin(false, 0, 0);
+    if (rc) return rc;
+    for (int64_t b0 = 0; b0 < n; b0 += net->chunk) {
+        const int64_t nb = std::min(net->chunk, n - b0);
+        rc = enqueue_net_trunk(net, hc.dev<const int8_t>(i_b) + b0 * c->N, nb, upto);
+        if (rc) return rc;
+        HIP_TRY(m3n::launch_net_widen(c->stream, nb * per, net->act[0], hc.dev<float>(o_x) + b0 * per));
+    }
+    return hc.finish();
+}
+
+}  // extern "C"
+
 // ---- network-guided device MCTS trees (m3_search_nn.hpp: the tree kernels) -------------
 struct m3_search_nn {
     m3_ctx* ctx = nullptr;
@@ -1814,6 +2030,31 @@ int m3_search_nn_run_linear(m3_search_nn* s, int32_t simulations, const float* d
         rc = enqueue_nn_commit(s, s->lin_values, s->lin_logits);
         if (rc) return rc;
         s->fed_linear += 1;
+    }
+    return M3_OK;
+}
+
+int m3_search_nn_run_net(m3_search_nn* s, int32_t simulations, m3_net* net) {
+    CHECK_ARG(s && simulations >= 0 && net, "bad arguments");
+    int rc = nn_state(s, "m3_search_nn_run_net", false);
+    if (rc) return rc;
+    m3_ctx* c = s->ctx;
+    if (net->ctx != c)
+        return set_err(M3_ERR_INVALID, "the net was made for a %d x %d x %d context, the search for %d x %d x %d (they "
+                       "must share one m3_ctx)", net->ctx->R, net->ctx->C, net->ctx->T, c->R, c->C, c->T);
+    rc = nn_fits(s, simulations);  // before anything is enqueued
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    int32_t left = simulations;
+    while (s->phase < 2 || left > 0) {
+        if (s->phase >= 2) --left;
+        rc = enqueue_nn_batch(s);
+        if (rc) return rc;
+        rc = enqueue_net_forward(net, s->R.ev_boards, s->R.ev_need, s->n, s->lin_values, s->lin_logits);
+        if (rc) return rc;
+        rc = enqueue_nn_commit(s, s->lin_values, s->lin_logits);
+        if (rc) return rc;
+        s->fed_device += 1;
     }
     return M3_OK;
 }

@@ -48,6 +48,8 @@ EXPORTS = [
     "m3_search_nn_create", "m3_search_nn_destroy", "m3_search_nn_set_roots", "m3_search_nn_batch",
     "m3_search_nn_feed_device", "m3_search_nn_feed", "m3_search_nn_run_linear", "m3_search_nn_result",
     "m3_search_nn_advance", "m3_search_nn_stats",
+    "m3_net_create", "m3_net_destroy", "m3_net_forward", "m3_net_forward_device", "m3_net_trunk",
+    "m3_search_nn_run_net",
 ]
 
 
@@ -137,6 +139,12 @@ def lib():
             "m3_search_nn_result": ([vp] * 10, i32),
             "m3_search_nn_advance": ([vp] * 6, i32),
             "m3_search_nn_stats": ([vp, vp], i32),
+            "m3_net_create": ([vp, i32, i32, i32, i32, i32, ctypes.c_double, vp, i64, vp], i32),
+            "m3_net_destroy": ([vp], i32),
+            "m3_net_forward": ([vp, vp, i64, vp, vp], i32),
+            "m3_net_forward_device": ([vp, vp, vp, i64, vp, vp], i32),
+            "m3_net_trunk": ([vp, vp, i64, i32, vp], i32),
+            "m3_search_nn_run_net": ([vp, i32, vp], i32),
         }
         for name, (args, res) in sig.items():
             fn = getattr(L, name, None)  # (an older A/B build may lack newer entry points;

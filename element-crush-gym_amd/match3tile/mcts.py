@@ -248,7 +248,9 @@ class NeuralNetworkMCTS:
 
     ``model(array[1, R, C]) -> (value, policy)`` as nn/mcts.py:46 calls it: ``policy`` holds one raw
     logit per action once flattened. It is called once for every node that is created and is not
-    terminal. ``exploration_weight`` is kept for parity; selection uses the node's ``n_actions``
+    terminal. A ``match3tile.net.ElementCrushNet`` as ``model`` is evaluated on the device
+    (``DeviceSearchNN(net=model)``), with the same results as calling it from the host.
+    ``exploration_weight`` is kept for parity; selection uses the node's ``n_actions``
     (abc/mcts.py:96). For many games at once use ``DeviceSearchNN`` itself."""
 
     def __init__(self, model, state, exploration_weight: float, simulations: int, verbose: bool = False):
@@ -259,6 +261,11 @@ class NeuralNetworkMCTS:
         self._simulations = simulations
         self._verbose = verbose
         A = 2 * state.cfg.rows * (state.cfg.columns - 1)
+        from .net import ElementCrushNet
+
+        if isinstance(model, ElementCrushNet):
+            self._search = DeviceSearchNN([state], simulations, net=model)
+            return
 
         def evaluator(boards, need):
             values, logits = np.zeros(1, np.float32), np.zeros((1, A), np.float32)

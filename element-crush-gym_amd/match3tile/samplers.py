@@ -71,16 +71,16 @@ def nn_mcts_task(model, seed=None, exploration_weight=3, simulations=100, moves=
 
 
 def nn_mcts_episodes(seeds, evaluator=None, weights=None, moves: int = 20, simulations: int = 100, rows: int = 9,
-                     columns: int = 9, types: int = 6):
+                     columns: int = 9, types: int = 6, net=None):
     """``nn_mcts_task`` for every seed at once, in lockstep: one ``DeviceSearchNN`` over all games, one
-    search and one re-rooting per move. ``evaluator`` / ``weights`` as ``DeviceSearchNN`` takes them
-    (a batch evaluator on the host, or the built-in linear evaluator on the device). Returns the episode
-    scores [len(seeds)]."""
+    search and one re-rooting per move. ``evaluator`` / ``weights`` / ``net`` as ``DeviceSearchNN`` takes
+    them (a batch evaluator on the host, or the built-in linear evaluator or an ``ElementCrushNet`` on the
+    device). Returns the episode scores [len(seeds)]."""
     from .search import DeviceSearchNN
 
     seeds = [int(s) for s in np.atleast_1d(seeds)]
     states = [BoardV2(moves, BoardConfig(rows=rows, columns=columns, types=types, seed=s)) for s in seeds]
-    ds = DeviceSearchNN(states, simulations, evaluator=evaluator, weights=weights)
+    ds = DeviceSearchNN(states, simulations, evaluator=evaluator, weights=weights, net=net)
     try:
         for _ in range(moves):
             ds()

@@ -216,17 +216,20 @@ def linear_evaluator(weights):
 
 
 class DeviceSearchNN:
-    """``DeviceSearchNN(states, simulations, evaluator=None, weights=None, node_capacity=None)``: the
+    """``DeviceSearchNN(states, simulations, evaluator=None, weights=None, node_capacity=None, net=None)``: the
     network-guided search of the reference (mctslib/nn/mcts.py: NNNode, NeuralNetworkMCTS), one tree per
     BoardV2 state in device memory (``m3_search_nn_*``, include/m3.h), all games in lockstep.
 
-    One of ``evaluator`` / ``weights`` is given:
+    One of ``evaluator`` / ``weights`` / ``net`` is given:
 
     - ``evaluator(boards: np.int8 [n, R, C], need: np.bool_ [n]) -> (values f32 [n], logits f32 [n, A])``
       is called once per round with every game's batch row on the host; rows with ``need`` False are
       ignored. Every created, non-terminal node is evaluated exactly once.
     - ``weights``: f32 ``[N, CH, A + 1]`` (``CH = onehot_width(types)``) of the built-in linear
       evaluator, which runs on the device: a whole ``__call__`` is enqueued without a host round trip.
+    - ``net``: a ``match3tile.net.ElementCrushNet`` of the states' board shape, the reference's
+      policy/value network on the device (``m3_search_nn_run_net``): as with ``weights`` a whole
+      ``__call__`` is enqueued without a host round trip. The search does not own the net.
     - ``evaluator=False``: the caller drives the rounds itself with ``batch`` and ``feed`` /
       ``feed_device``, the two construction batches included (``run`` and ``__call__`` are not for it).
 
@@ -242,16 +245,20 @@ class DeviceSearchNN:
     bytes (9x9x6: 725)."""
 
     def __init__(self, states: Sequence, simulations: int, evaluator=None, weights=None,
-                 node_capacity: Optional[int] = None):
+                 node_capacity: Optional[int] = None, net=None):
         states = list(states)
         if not states:
             raise ValueError("DeviceSearchNN needs at least one state")
-        if (evaluator is None) == (weights is None):
-            raise ValueError("DeviceSearchNN needs exactly one of evaluator= and weights=")
+        if (evaluator is not None) + (weights is not None) + (net is not None) != 1:
+            raise ValueError("DeviceSearchNN needs exactly one of evaluator=, weights= and net=")
         cfg = states[0].cfg
         shape = (cfg.rows, cfg.columns, cfg.types)
         if any((s.cfg.rows, s.cfg.columns, s.cfg.types) != shape for s in states):
             raise ValueError("DeviceSearchNN needs states of one board shape")
+        if net is not None and (net.cfg.rows, net.cfg.columns, net.cfg.types) != shape:
+            raise ValueError(f"net= of board shape {(net.cfg.rows, net.cfg.columns, net.cfg.types)}, the states are "
+                             f"{shape}")
+        self._net = net
         self._ctx = ctx = _native.context(*shape)
         self._cfgs = [s.cfg for s in states]
         self._evaluator = evaluator
@@ -333,6 +340,11 @@ class DeviceSearchNN:
         if self._w is not None:
             with self._ctx._lock:
                 _native.check(_native.lib().m3_search_nn_run_linear(self._h, sims, self._w.ptr))
+            self._construction = 0
+            return
+        if self._net is not None:
+            with self._ctx._lock:
+                _native.check(_native.lib().m3_search_nn_run_net(self._h, sims, self._net.handle))
             self._construction = 0
             return
         while self._construction or sims:

@@ -304,6 +304,50 @@ int m3_search_nn_advance(m3_search_nn *s, const int32_t *actions, int8_t *out_bo
  * built-in linear evaluator. Blocks. */
 int m3_search_nn_stats(m3_search_nn *s, uint64_t out[6]);
 
+/* ---- the policy/value network: the reference's ElementCrush (elementCrush.py:51-97,
+ * elementGOModules.py) in inference form, on the device (csrc/m3_net.hip; DESIGN.md §4.4 has the
+ * arithmetic model). For a context of rows x columns x types: P = rows * columns, A = the action
+ * space, CH = 2^(ceil(log2(types)) + 2).
+ *   one_hot(cell, CH): a cell < 0 or >= CH is the zero vector (any int8 is accepted)
+ *   stem    3x3 SAME conv CH -> F with bias, BatchNorm, ReLU
+ *   tower   `layers` x (conv, BN, ReLU, conv, BN, + residual, ReLU), 3x3 SAME F -> F with bias
+ *   value   1x1 conv F -> 1, BN, ReLU, flatten, dense [P -> F], ReLU, dense [F -> 1], ReLU
+ *   policy  1x1 conv F -> 2, BN, ReLU, flatten (NHWC: (r * columns + c) * 2 + ch), dense [2P -> A]:
+ *           raw logits
+ * BatchNorm uses the stored statistics, y = (x - mean) * scale / sqrt(var + bn_eps) + bias, folded
+ * in float64 into the convolution before it. The tower runs on the bf16 matrix cores with float32
+ * accumulation (weights rounded once to bf16, activations stored as bf16); stem and heads are float32.
+ * A board's outputs do not depend on n, on its index in the batch or on the need mask.
+ *
+ * blob: the weights as float32, concatenated in this order (conv kernels [kh][kw][in][out], dense
+ * kernels [in][out]; "bn" = scale, bias, mean, var, each [out]):
+ *   stem kernel [3][3][CH][F], bias [F], bn;
+ *   per residual layer: conv1 kernel [3][3][F][F], bias [F], bn1; conv2 kernel, bias, bn2;
+ *   value: conv kernel [1][1][F][1], bias [1], bn; dense1 kernel [P][F], bias [F]; dense2 kernel
+ *   [F][1], bias [1];
+ *   policy: conv kernel [1][1][F][2], bias [2], bn; dense kernel [2P][A], bias [A].
+ * features: a multiple of 32 in 32..512 (else M3_ERR_UNSUPPORTED); layers >= 0. rows, columns and
+ * types must be the context's, blob_len the exact length (M3_ERR_INVALID). The workspace (two bf16
+ * activation buffers of at most 64 MiB each) is allocated here; larger batches run in chunks of boards. */
+typedef struct m3_net m3_net;
+int m3_net_create(m3_ctx *ctx, int32_t rows, int32_t columns, int32_t types, int32_t layers, int32_t features,
+                  double bn_eps, const float *blob, int64_t blob_len, m3_net **out);
+int m3_net_destroy(m3_net *net);
+/* Host arrays: boards int8 [n][P] -> values f32 [n], logits f32 [n][A]. Blocks. n = 0 is allowed. */
+int m3_net_forward(m3_net *net, const int8_t *boards, int64_t n, float *values, float *logits);
+/* The same on device arrays, enqueued on the context stream; does not wait. d_need (nullable,
+ * uint8 [n]): rows with need == 0 are not written. */
+int m3_net_forward_device(m3_net *net, const int8_t *d_boards, const uint8_t *d_need, int64_t n, float *d_values,
+                          float *d_logits);
+/* Feature extraction: the trunk's activations after the stem (upto = 0) or after residual layer
+ * `upto` (1..layers), widened to float32, out [n][rows][columns][F] (host). Blocks. */
+int m3_net_trunk(m3_net *net, const int8_t *boards, int64_t n, int32_t upto, float *out);
+/* m3_search_nn_run_linear with the network as the evaluator: the pending construction batches and
+ * `simulations` rounds with no host round trip (counted in m3_search_nn_stats out[4]). The state and
+ * capacity errors are the same; M3_ERR_INVALID if the net was not made on the search's context (so
+ * for another board shape). */
+int m3_search_nn_run_net(m3_search_nn *s, int32_t simulations, m3_net *net);
+
 /* ---- device-resident batched env: n x Match3Env (env.py:8-65) ----------- */
 
 /* num_moves / env_goal as Match3Env(num_moves=20, env_goal=500) (env.py:15-16). */
